@@ -11,11 +11,14 @@ path (radix partition of the rows into (window, region) bins, the region-owned m
 update-mode state that also writes the update-mode rows) or, for low-cardinality batches, table mode (two LDS
 aggregation passes first); in-place densification of the rows (k_fill_gaps), eviction (whole window tables
 released), and the latest-position flags + compaction.
-Every step is a NEW micro-batch: its timestamps are the previous step's + 15 min (precomputed before the
-timed region), so the stream advances, windows close and are evicted, and no row is late.  A second leg
-(`state_read_leg`, N=1 only) times the regime where batches update open windows: 1 minute of event time per step,
-advancing 1 minute, res 7.
+Every step is a NEW micro-batch: its timestamps are the previous step's + 15 min (resident before the step
+runs and computed outside the clock: before the timed region, and for steps beyond TS_POOL between two steps), so the stream advances, windows close and are evicted, and no row is late.
 For N>1 each rank runs the sharded path (mobheat.distributed: RCCL all-to-all of partials by owner).
+
+A plain run does that and nothing else: set up, warm up, time the --steps steps, write the last step's outputs if
+--dump-outputs DIR is given, print the result line.  --full adds, after it (N=1 only), a second leg (`state_read_leg`)
+that times the regime where batches update open windows: 1 minute of event time per step, advancing 1 minute, res 7;
+and the CPU baselines (`cpu_baseline`: the oracle's C restatement of the micro-batch on this host).
 
 Prints ONE JSON line (rank 0).  See DESIGN.md for the roofline's algorithmic-byte accounting.
 """
@@ -289,27 +292,118 @@ class _Tiles:
         return len(self.cell)
 
 
-def run_leg(args, n, res, span_us, advance_us, seed, dev, local, world, rank, arena_bytes=0, sharded=False):
+TS_POOL = 32   # timestamp buffers resident at once (run_leg): 25.6 GB at 1e8 events
+DUMP_SEED = 0x5EED0B5E9C0FFEE5   # picks the dumped sample of the tile rows by key (dump_outputs)
+DUMP_TILE_BYTES = 48 << 20       # of --dump-outputs' 64 MB: the tile rows' eight float64 columns ...
+DUMP_LATEST_BYTES = 8 << 20      # ... and the latest rows
+
+
+def _i64(x):
+    """A 64-bit constant as the signed value torch's int64 arithmetic (wrapping) takes."""
+    x &= (1 << 64) - 1
+    return x - (1 << 64) if x >> 63 else x
+
+
+def _sample_hash(a, b=None):
+    """24 well-mixed bits per element of the int64 tensor a (and b): a fixed, seeded function of the values alone."""
+    x = a ^ _i64(DUMP_SEED)
+    if b is not None:
+        x = x * _i64(0x9E3779B97F4A7C15) + b
+    for mul in (0xFF51AFD7ED558CCD, 0xC4CEB9FE1A85EC53):
+        x = (x ^ ((x >> 33) & 0x7FFFFFFF)) * _i64(mul)
+    return (x >> 40) & 0xFFFFFF
+
+
+def _sample_shift(rows, row_bytes, budget):
+    """The smallest k with rows / 2^k rows of row_bytes each expected within the budget (0: every row)."""
+    k = 0
+    while (rows >> k) * row_bytes > budget * 7 // 8 and k < 24:   # (1/8 of the budget: the sample's own scatter)
+        k += 1
+    return k
+
+
+def dump_outputs(path, out, dev):
+    """--dump-outputs: what the timed path returned for its last step (the HmBatchOut of hm_process_batch / the stage
+    API: the update-mode tile rows and the latest rows, on the device), written as path/<name>.npy in float64, every
+    value exact in it.  The library emits the tile rows in no fixed order, so they are written sorted by (window start,
+    cell); of more rows than fit the size limit, a sample chosen by a seeded hash of the row's key (tiles: cell and
+    window start; latest rows: the row index) -- the same keys in every run and every build.
+      cell_hi, cell_lo          the H3 index's upper and lower 32 bits
+      window_start_us, count, avg_speed, speed_null, avg_lon, avg_lat   the tile rows' other columns
+      latest_rows               the input rows holding their vehicle's latest position, ascending
+      counts                    n_tiles, n_latest, n_in, n_valid, n_late, n_state, batch_max_event_ms, watermark_ms,
+                                late_watermark_ms, n_partials, then the two samples' shifts k (rows kept: hash < 2^(24-k))
+    """
+    from mobheat import _lib
+    lib = _lib.load()
+    os.makedirs(path, exist_ok=True)
+
+    def column(ptr, n, dtype):
+        """n elements at a device pointer of the library's, copied into a tensor (device to device)."""
+        t = torch.empty(max(n, 1), dtype=dtype, device=dev)
+        if n:
+            _lib.check(lib.hm_memcpy(t.data_ptr(), ptr, n * t.element_size(), 2), None, "hm_memcpy")
+        return t[:n]
+
+    nt, nl = int(out.n_tiles), int(out.n_latest)
+    kt = _sample_shift(nt, 8 * 8, DUMP_TILE_BYTES)
+    kl = _sample_shift(nl, 8, DUMP_LATEST_BYTES)
+    cell, ws = column(out.cell, nt, torch.int64), column(out.window_start_us, nt, torch.int64)
+    keep = torch.nonzero(_sample_hash(cell, ws) < (1 << (24 - kt))).flatten()
+    c = cell[keep].cpu().numpy().view(np.uint64)
+    cols = {"cell_hi": c >> np.uint64(32), "cell_lo": c & np.uint64(0xFFFFFFFF), "window_start_us": ws[keep].cpu().numpy()}
+    del cell, ws
+    for name, dtype in (("count", torch.int64), ("avg_speed", torch.float64), ("speed_null", torch.uint8),
+                        ("avg_lon", torch.float64), ("avg_lat", torch.float64)):
+        cols[name] = column(getattr(out, name), nt, dtype)[keep].cpu().numpy()
+    order = np.lexsort((c, cols["window_start_us"]))
+    for name, a in cols.items():
+        np.save(os.path.join(path, name + ".npy"), a[order].astype(np.float64))
+    rows = column(out.latest_row, nl, torch.int64)
+    rows = rows[_sample_hash(rows) < (1 << (24 - kl))].cpu().numpy()
+    np.save(os.path.join(path, "latest_rows.npy"), np.sort(rows).astype(np.float64))
+    np.save(os.path.join(path, "counts.npy"), np.array(
+        [nt, nl, out.n_in, out.n_valid, out.n_late, out.n_state, out.batch_max_event_ms, out.watermark_ms,
+         out.late_watermark_ms, out.n_partials, kt, kl], np.float64))
+
+
+def run_leg(args, n, res, span_us, advance_us, seed, dev, local, world, rank, arena_bytes=0, sharded=False, dump=None):
     """Warmup + exactly K timed steps (barrier + synchronize on both sides, max over ranks); per-stage HIP-event
-    times (the library's events on its own stream) and algorithmic bytes of the timed steps."""
+    times (the library's events on its own stream) and algorithmic bytes of the timed steps.  dump: a directory that
+    receives the last timed step's outputs (dump_outputs), after the timed region."""
     import mobheat
     from mobheat.distributed import LibStages, ShardedHeatmap
     total_steps = args.warmup + args.steps
-    data = gen_batch(n, total_steps, seed=seed, dev=dev, span_us=span_us, advance_us=advance_us)
+    # step s's timestamps are resident before it runs, in one of at most TS_POOL buffers (8 B per event each: one per
+    # step of a long run would not fit the device); a run of more steps advances a buffer, once its step is over, to
+    # the step TS_POOL later, outside the clock
+    pool = min(total_steps, TS_POOL)
+    data = gen_batch(n, pool, seed=seed, dev=dev, span_us=span_us, advance_us=advance_us)
     eng = mobheat.HeatmapEngine(h3_res=res, device=local, batch_capacity_hint=n, state_arena_bytes=arena_bytes,
                                 shard=(rank, world) if world > 1 else None)
     sharded = ShardedHeatmap(LibStages(eng), dev) if (world > 1 or sharded) else None
 
     def step(s):
-        ptrs = dict(n=n, lat=data["lat"].data_ptr(), lon=data["lon"].data_ptr(), ts_us=data["ts"][s].data_ptr(),
+        ptrs = dict(n=n, lat=data["lat"].data_ptr(), lon=data["lon"].data_ptr(), ts_us=data["ts"][s % pool].data_ptr(),
                     speed=data["speed"].data_ptr(), speed_valid=data["sv"].data_ptr(), vkey=data["vkey"].data_ptr(),
                     row_valid=data["rv"].data_ptr())
         if sharded is None:
             return eng.process_batch_device(s, **ptrs)
         return sharded.process_batch(s, ptrs)
 
+    def refill(s):
+        """Step s is over (the library call returns after its last read of the inputs): its buffer becomes step
+        s + pool's.  Returns the seconds this took (0.0 when every step has a buffer of its own)."""
+        if s + pool >= total_steps:
+            return 0.0
+        r0 = time.perf_counter()
+        data["ts"][s % pool] += pool * advance_us
+        torch.cuda.current_stream().synchronize()
+        return time.perf_counter() - r0
+
     for s in range(args.warmup):
         step(s)
+        refill(s)
     torch.cuda.synchronize()
     if dist.is_initialized():
         dist.barrier()
@@ -320,10 +414,12 @@ def run_leg(args, n, res, span_us, advance_us, seed, dev, local, world, rank, ar
     host = []   # per step: the library call's host side (wall, syncs, allocations; single GPU)
     phases = []   # per step (sharded path): host wall ms of each stage phase (distributed.ShardedHeatmap)
     counts = None
+    last = None
+    refilling = 0.0   # seconds of the timed region spent preparing later steps' timestamps (refill), not timed
     t0 = time.perf_counter()
     for s in range(args.warmup, total_steps):
         ts0 = time.perf_counter()
-        step(s)
+        last = step(s)
         step_ms.append((time.perf_counter() - ts0) * 1e3)
         if sharded is None:
             host.append(eng.last_host_timings())
@@ -335,15 +431,18 @@ def run_leg(args, n, res, span_us, advance_us, seed, dev, local, world, rank, ar
             kt[k] += max(tm[k], 0.0)
         for k, v in stage_bytes(n, counts, world, staged=sharded is not None).items():
             kb[k] += v
+        refilling += refill(s)
     torch.cuda.synchronize()
     if dist.is_initialized():
         dist.barrier()
     torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - refilling
     if dist.is_initialized():
         e = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
+    if dump and last is not None:
+        dump_outputs(dump, last, dev)
     eng.close()
     del data
     torch.cuda.empty_cache()
@@ -378,6 +477,12 @@ def main():
                     help="run the multi-GPU stage path (mobheat.distributed over torch.distributed) even at --gpus 1: "
                          "at N=1 the exchange is RCCL's all-to-all of a rank with itself (the N>1 code path on one GPU)")
     ap.add_argument("--c1-baseline", action="store_true", help="only the C1 CPU baseline (BASELINE.md section 2)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need: the state-read leg "
+                         "(unless --no-state-leg) and the CPU baselines (unless --no-cpu-baseline); one GPU, not --sharded")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs (rank 0's) as DIR/<name>.npy, float64, at most 64 MB "
+                         "(dump_outputs)")
     args = ap.parse_args()
     if args.c1_baseline:
         print(json.dumps(cpu_baseline_c1()), flush=True)
@@ -407,7 +512,8 @@ def main():
 
     n = args.events
     K = args.steps
-    A = run_leg(args, n, args.res, SPAN_US, SPAN_US, 1 + 7919 * rank, dev, local, world, rank, sharded=sharded)
+    A = run_leg(args, n, args.res, SPAN_US, SPAN_US, 1 + 7919 * rank, dev, local, world, rank, sharded=sharded,
+                dump=args.dump_outputs if rank == 0 else None)
     elapsed, avg_ms, kb, c = A["elapsed"], A["kt"], A["kb"], A["counts"]
     ms_step = elapsed / K * 1e3
     # Roofline of the dominant stage by time, priced on HBM (the metric's "% HBM peak"), with the PMC-counted
@@ -490,7 +596,7 @@ def main():
     if A["phases"]:   # the sharded path: median host wall ms per stage phase (rank 0)
         out["stage_phase_ms"] = A["phases"]
     B = None
-    if world == 1 and not sharded and not args.no_state_leg:
+    if args.full and world == 1 and not sharded and not args.no_state_leg:
         # second leg: the state-read regime of the reference's ~2-s trigger (README.md:134-135) -- each micro-batch
         # holds 1 minute of event time and the stream advances 1 minute per step, so consecutive batches update the
         # same open windows and the merge reads existing state lines.  res 7 (configs[1]'s resolution): 1e8 events
@@ -510,7 +616,7 @@ def main():
             "tiles_last_step": B["counts"]["tiles"], "state_keys_created_last_step": B["counts"]["state_new"],
             "step_frac": bb / (bms * 1e-3) / 1e9 / HBM_PEAK_GBS, "step_s8d": s8d(n, B["counts"], bms),
             "slowest_step": slowest_step(B)}
-    if rank == 0 and world == 1 and not sharded and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not sharded and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_sample, args.res)
         out["cpu_baseline"]["c1"] = cpu_baseline_c1()
     if rank == 0:

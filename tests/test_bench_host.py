@@ -48,6 +48,52 @@ def test_stage_bytes_multi_gpu_owner():
     assert s["partition"] == 0 and s["ingest"] == 43 * n + 32 * S and s["send"] == 64 * S
 
 
+def test_full_and_dump_outputs_options(monkeypatch, capsys):
+    """The command line has --full and --dump-outputs DIR."""
+    import pytest
+    monkeypatch.setattr("sys.argv", ["bench.py", "--help"])
+    with pytest.raises(SystemExit) as e:
+        _bench().main()
+    assert e.value.code == 0
+    usage = capsys.readouterr().out
+    assert "--full" in usage and "--dump-outputs DIR" in usage
+
+
+def test_dump_sample_shift_keeps_the_sample_within_its_budget():
+    b = _bench()
+    assert b._sample_shift(4000, 64, b.DUMP_TILE_BYTES) == 0          # everything fits: every row
+    assert b._sample_shift(0, 64, b.DUMP_TILE_BYTES) == 0
+    n = 97_590_394                                                     # the bench's tiles per step
+    k = b._sample_shift(n, 64, b.DUMP_TILE_BYTES)
+    assert (n >> k) * 64 <= b.DUMP_TILE_BYTES * 7 // 8 < (n >> (k - 1)) * 64
+    # all files together stay under 64 MB, with 1/8 of each budget left for the sample's own scatter
+    assert b.DUMP_TILE_BYTES + b.DUMP_LATEST_BYTES + 12 * 8 + 10 * 128 < 64_000_000
+
+
+def test_dump_sample_hash_depends_on_the_key_alone():
+    """The sample of the tile rows is chosen by a hash of (cell, window start): the same keys whatever order the rows
+    come in, and close to the fraction asked for on keys as regular as H3 indexes of one resolution are (their low 21
+    bits all ones at res 8, three window starts)."""
+    import numpy as np
+    import torch
+    b = _bench()
+    n = 200_000
+    rng = np.random.default_rng(5)
+    cell = torch.from_numpy((0x0882A10000000000 + (rng.permutation(1 << 20)[:n].astype(np.int64) << 21)) | 0x1FFFFF)
+    ws = torch.from_numpy(1759572000_000000 + 300_000_000 * rng.integers(0, 3, n))
+    h = b._sample_hash(cell, ws)
+    assert int(h.min()) >= 0 and int(h.max()) < 1 << 24
+    p = torch.from_numpy(rng.permutation(n))
+    assert torch.equal(b._sample_hash(cell[p], ws[p]), h[p])
+    assert not torch.equal(b._sample_hash(cell, ws + 300_000_000), h)   # the window start is part of the key
+    kept = int((h < (1 << 21)).sum())                                   # k = 3: one key in eight
+    sd = (n * (1 / 8) * (7 / 8)) ** 0.5                                 # binomial; 5 sd: ~6e-7 two-sided
+    assert abs(kept - n / 8) < 5 * sd, (kept, n / 8, sd)
+    rows = torch.arange(n, dtype=torch.int64)                           # latest rows: hashed by the row index
+    kept = int((b._sample_hash(rows) < (1 << 21)).sum())
+    assert abs(kept - n / 8) < 5 * sd, (kept, n / 8, sd)
+
+
 def test_stage_bytes_self_held_records():
     """The records of the bins a rank owns stay in its slabs (binned): only their keys are read (census), 8 B each;
     the bench's --sharded run prices the stage API at world 1 too."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Split a rocprofv3 --kernel-trace of `bench.py` by leg: the bench leg's dispatches come first (warmup + timed steps
+"""Split a rocprofv3 --kernel-trace of `bench.py --full` by leg: the bench leg's dispatches come first (warmup + timed steps
 at res 8), then the state-read leg's (res 7).  The boundary is the first k_ingest dispatch after the bench leg's
 steps (warmup + steps of the command line).  Prints, per leg, each kernel's calls and average duration.
 
