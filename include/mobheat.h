@@ -26,6 +26,8 @@
  *                                   statement {q, u: {$set: doc}, multi, upsert} per emitted tile, BSON-encoded
  *                                   on the GPU exactly as pymongo encodes the reference's UpdateOne.
  *   hm_encode_position_updates   -- the positions half (:198-235): one positions_latest statement per latest row.
+ *   hm_live_windows / hm_window_rollup -- the web API's read of the latest window's tiles (app.py:45-69), from the
+ *                                   engine's state instead of MongoDB, at any H3 resolution <= H3_RES.
  */
 #ifndef MOBHEAT_H
 #define MOBHEAT_H
@@ -35,7 +37,7 @@
 extern "C" {
 #endif
 
-#define HM_ABI_VERSION 11
+#define HM_ABI_VERSION 12
 
 /* error codes */
 #define HM_OK 0
@@ -441,6 +443,27 @@ int hm_cells_to_boundary(const uint64_t *cells, int64_t n, int32_t memory, int32
                          int32_t *nverts);
 /* Host execution of the same device code (no GPU; the CPU tests compare it with the oracle). */
 int hm_selftest_cells_to_boundary_host(const uint64_t *cells, int64_t n, double *lat, double *lng, int32_t *nverts);
+
+/* ---- read side without MongoDB: the tile state's windows at any zoom level (reference app.py:45-69 reads the latest
+ * window's tiles from the tiles collection; here they come straight from the state the engine holds) ----
+ * live windows of the tile state, ascending by start: *n = count, up to cap written; keys[i] = live keys of window i
+ * (either array may be NULL).  "Live" = not yet evicted by the watermark. */
+int hm_live_windows(hm_ctx *ctx, int64_t *window_start_us, int64_t *keys, int64_t cap, int64_t *n);
+/* the tiles of live window window_start_us at resolution res (0..h3_res): one record per distinct parent cell with
+ * the cumulative count / n_speed / sums of its children (avg = sum / count on the caller's side; reserved = 0);
+ * res == h3_res: the window's own keys.  One GPU pass over the window's table.  Records are in no particular order.
+ * Library-owned (device or pinned host per out_memory: HM_MEM_DEVICE / HM_MEM_HOST), valid until the next call on the
+ * context.  A window that is not live: *n = 0.  res outside 0..h3_res: HM_E_INVALID; between stage calls: HM_E_STATE.
+ * Reads the state only (hm_state_version, the next batch and a checkpoint export in progress are unaffected); a
+ * repeated call with the same window and resolution allocates nothing.
+ * On a shard context (hm_config.shard_count > 1) the records cover the keys that rank owns: a parent whose children
+ * are spread over several ranks appears once per such rank, and the caller adds the records of equal cell (they carry
+ * sums, not averages, for that reason).  The library does not combine across ranks. */
+int hm_window_rollup(hm_ctx *ctx, int64_t window_start_us, int32_t res, int32_t out_memory,
+                     const hm_state_rec **recs, int64_t *n);
+/* host execution of the kernels' h3_cell_to_parent (no GPU): out[i] = upstream cellToParent(cells[i], res) for
+ * res <= the cells' resolution (resolution field := res, digits res+1..15 := 7) */
+int hm_selftest_cell_to_parent(const uint64_t *cells, int64_t n, int32_t res, uint64_t *out);
 
 /* Counts of the last hm_process_batch / stage batch (up to n of them): [0] keys created in the tile state, [1] partial
  * records merged (direct path: aggregated rows; table mode: ~ distinct keys; stage API: the records this rank

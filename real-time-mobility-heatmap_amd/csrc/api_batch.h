@@ -205,7 +205,7 @@ void hm_destroy(hm_ctx *ctx) {
                       &ctx->jd_bytes, &ctx->jd_offs, &ctx->jd_scratch, &ctx->jd_lat, &ctx->jd_lon, &ctx->jd_ts, &ctx->jd_speed,
                       &ctx->jd_sv, &ctx->jd_rv, &ctx->jd_vkey, &ctx->jd_poff, &ctx->jd_plen, &ctx->jd_voff, &ctx->jd_vlen,
                       &ctx->jd_un, &ctx->jd_unrows, &ctx->jd_patch,
-                      &ctx->lb_set, &ctx->lb_list, &ctx->dense};
+                      &ctx->lb_set, &ctx->lb_list, &ctx->dense, &ctx->ru_tab, &ctx->ru_out};
     for (DevBuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (hm_ctx::Dict *d : {&ctx->jd_prov, &ctx->jd_veh}) {
@@ -232,7 +232,7 @@ void hm_destroy(hm_ctx *ctx) {
     if (ctx->dfused.tab) (void)hipFree(ctx->dfused.tab);
     if (ctx->dfull.tab) (void)hipFree(ctx->dfull.tab);
     void *hbufs[] = {ctx->h_cell, ctx->h_ws, ctx->h_cnt, ctx->h_sp, ctx->h_spn, ctx->h_lon, ctx->h_lat, ctx->h_rows,
-                     ctx->h_td_bytes, ctx->h_td_off};
+                     ctx->h_td_bytes, ctx->h_td_off, ctx->h_ru};
     for (void *p : hbufs)
         if (p) (void)hipHostFree(p);
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);

@@ -134,6 +134,10 @@ struct hm_ctx {
     Dict jd_prov, jd_veh;
     DevBuf ar_bits[6], ar_offs[2], ar_data[2];   // hm_arrow_columns: validity bitmaps, the string columns' offsets / bytes
     DevBuf lb_set, lb_list;   // hm_last_latest_buckets
+    // hm_window_rollup (api_read.h): the zeroed parent table, the compacted records, their pinned host copy
+    DevBuf ru_tab, ru_out;
+    void *h_ru = nullptr;
+    size_t h_ru_cap = 0;
     DevBuf keys;                     // k_ingest's event key per row (kernels.h ekey)
     // k_ingest's fused binning (large direct-path batches): the bins' cursors (RP_BINS + 1 u32: the last stays 0, so
     // that their exclusive scan ends with the total) and the slab capacity; the slabs are parts_sorted
@@ -244,6 +248,7 @@ constexpr int FULL_USED_WORD = 240;   // used-slot count of the full dedup table
 constexpr int SLOW_WORD = 252;
 constexpr size_t REG_BLOCK_BYTES = 2 * (WREG_SLOTS + 1) * 8 + sizeof(DevStats);   // d_wreg | d_wcount | d_st (hm_create)   // number of k_ingest fast-path exceptions of the current batch
 constexpr int REGROW_WORD = 251; // records dumped by k_dump_gen
+constexpr int ROLLUP_WORD = 249; // 249-250: hm_window_rollup's parents emitted, parent-table overflow
 constexpr int GIVEUP_WORD = 232;
 constexpr int GAPS_WORD = 242;   // 242-243: totals of the gap / donor scans
 constexpr int POSBAD_WORD = 241; // position statements: rows outside the caller's dictionaries

@@ -10,8 +10,9 @@
 //   k_ingest.h      the per-event pass (k_ingest: filter + latLngToCell + window + late test + dedup max + event key)
 //   k_json.h        Kafka values -> columns, string dictionaries
 //   k_stage.h       multi-GPU exchange helpers
+//   k_rollup.h      read side: one window's tiles rolled up to a coarser resolution (k_rollup, k_rollup_emit)
 //   host_ctx.h      the context, allocation, per-window tables, launchers;  host_batch.h: the batch phases
-//   api_*.h         the C ABI of include/mobheat.h (batch, UDF/read side, stage API, checkpoint, sink, JSON, self-tests)
+//   api_*.h         the C ABI of include/mobheat.h (batch, UDF/read side, stage API, checkpoint, sink, JSON, window reads, self-tests)
 //
 // Pipeline per batch (one HIP stream per context; every arithmetic step runs on the GPU):
 //   k_ingest      filter (heatmap_stream.py:96-104) + H3 latLngToCell UDF (:65-75,105) + tumbling window (:115) +
@@ -77,6 +78,7 @@ static hipError_t upload_tables() {
 #include "k_ingest.h"
 #include "k_json.h"
 #include "k_stage.h"
+#include "k_rollup.h"
 #include "host_ctx.h"
 #include "host_batch.h"
 #include "host_pipe.h"
@@ -89,6 +91,7 @@ extern "C" {
 #include "api_state.h"
 #include "api_sink.h"
 #include "api_json.h"
+#include "api_read.h"
 #include "api_selftest.h"
 
 }  // extern "C"

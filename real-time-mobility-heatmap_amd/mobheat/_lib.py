@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # MOBHEAT_LIB: load another build of the same ABI (kernel variants under csrc/variants/ for tuning runs)
 LIB_PATH = os.environ.get("MOBHEAT_LIB") or os.path.normpath(os.path.join(_HERE, "..", "csrc", "libmobheat.so"))
 
-HM_ABI_VERSION = 11
+HM_ABI_VERSION = 12
 HM_MEM_HOST = 0
 HM_MEM_DEVICE = 1
 HM_MEM_HOST_STREAM = 2
@@ -154,6 +154,9 @@ SIGNATURES = {
     "hm_selftest_json_records": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                          c_vp, c_vp]),
     "hm_selftest_decimal_to_double": (c_i32, [c_vp, c_vp, c_i64, c_vp]),
+    "hm_live_windows": (c_i32, [c_vp, c_vp, c_vp, c_i64, _P(c_i64)]),
+    "hm_window_rollup": (c_i32, [c_vp, c_i64, c_i32, c_i32, _P(c_vp), _P(c_i64)]),
+    "hm_selftest_cell_to_parent": (c_i32, [c_vp, c_i64, c_i32, c_vp]),
     "hm_abi_version": (c_i32, []),
 }
 

@@ -251,6 +251,52 @@ class HeatmapEngine:
         not touch the state)."""
         return int(self._lib.hm_state_version(self._ctx))
 
+    # ---- the state's windows read back at any zoom level (hm_live_windows / hm_window_rollup) ----
+    def live_windows(self):
+        """(window_start_us int64[], keys int64[]) of the windows the tile state holds (those the watermark has not
+        evicted), ascending by start; keys = the live (cell, window) keys of each."""
+        n = ctypes.c_int64()
+        check(self._lib.hm_live_windows(self._ctx, None, None, 0, ctypes.byref(n)), self._ctx, "hm_live_windows")
+        ws, keys = np.zeros(n.value, np.int64), np.zeros(n.value, np.int64)
+        if n.value:
+            check(self._lib.hm_live_windows(self._ctx, ptr(ws), ptr(keys), ws.size, ctypes.byref(n)), self._ctx,
+                  "hm_live_windows")
+        return ws, keys
+
+    def window_records(self, window_start_us=None, res=None, copy=True):
+        """The tiles of one live window rolled up on the GPU to H3 resolution res <= h3_res (None: h3_res, the window's
+        own keys): STATE_REC_DTYPE records, one per distinct parent cell, with the cumulative count / n_speed / sums
+        of its children, in no particular order.  window_start_us None = the newest live window; a window that is
+        not live gives no record.  copy=False: a view of the library's pinned buffer, valid until the next call on
+        this engine.  On a shard engine: the keys this rank owns (add the records of equal cell across ranks)."""
+        res = self.h3_res if res is None else int(res)
+        if window_start_us is None:
+            ws, _ = self.live_windows()
+            if ws.size == 0:
+                return np.zeros(0, STATE_REC_DTYPE)
+            window_start_us = ws[-1]
+        p, n = ctypes.c_void_p(), ctypes.c_int64()
+        check(self._lib.hm_window_rollup(self._ctx, int(window_start_us), res, HM_MEM_HOST, ctypes.byref(p),
+                                         ctypes.byref(n)), self._ctx, "hm_window_rollup")
+        if n.value == 0:
+            return np.zeros(0, STATE_REC_DTYPE)
+        raw = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)),
+                                    shape=(n.value * STATE_REC_DTYPE.itemsize,))
+        recs = raw.view(STATE_REC_DTYPE)
+        return recs.copy() if copy else recs
+
+    def window_tiles(self, window_start_us=None, res=None):
+        """window_records as the TileRows process_batch returns: avg_speed = sum_speed / n_speed (0.0 and speed_null
+        where no child had a speed), avg_lat / avg_lon = the sums over count."""
+        r = self.window_records(window_start_us, res, copy=False)
+        has = r["n_speed"] > 0
+        avg_speed = np.zeros(r.size)
+        np.divide(r["sum_speed"], r["n_speed"], out=avg_speed, where=has)
+        cnt = r["count"].astype(np.int64)
+        ws = r["window_start_us"].astype(np.int64)
+        return TileRows(cell=r["cell"].astype(np.uint64), window_start_us=ws, window_end_us=ws + self.tile_us, count=cnt,
+                        avg_speed=avg_speed, speed_null=~has, avg_lon=r["sum_lon"] / cnt, avg_lat=r["sum_lat"] / cnt)
+
     def _export_buffer(self, n, reuse, raw_out=None):
         """n state records of host memory: a fresh array, or (reuse) a view of the engine's page-locked export buffer --
         valid until the next reuse export (a device-to-host copy into pageable memory ran at ~10 GB/s: 66 ms of a

@@ -61,3 +61,37 @@ def tiles_latest_collection(docs, device=0):
                          "properties": props})
     return {"type": "FeatureCollection", "features": features}
 
+
+def tile_docs_from_engine(engine, res=None, city="boston", tz=None, window_start_us=None):
+    """The tile documents of one live window (None: the newest) as the sink stores them (cellId, windowStart,
+    windowEnd, count, avgSpeedKmh, centroid, city, grid), read from the engine's state rolled up to resolution res
+    (HeatmapEngine.window_tiles) -- no MongoDB in between.  windowStart / windowEnd are the naive local datetimes the
+    sink writes (stream._spark_datetime: the process's zone), or zone tz's wall time when a tzinfo is given."""
+    import datetime as _dt
+
+    from .stream import _spark_datetime
+
+    def when(us):
+        us = int(us)
+        if tz is None:
+            return _spark_datetime(us)
+        return _dt.datetime.fromtimestamp(us // 1000000, tz).replace(tzinfo=None, microsecond=us % 1000000)
+    res = engine.h3_res if res is None else int(res)
+    t = engine.window_tiles(window_start_us, res)
+    docs = []
+    for k in range(len(t)):
+        docs.append({"city": city, "grid": f"h3r{res}", "cellId": format(int(t.cell[k]), "x"),
+                     "windowStart": when(t.window_start_us[k]), "windowEnd": when(t.window_end_us[k]),
+                     "count": int(t.count[k]), "avgSpeedKmh": 0.0 if t.speed_null[k] else float(t.avg_speed[k]),
+                     "centroid": {"type": "Point", "coordinates": [float(t.avg_lon[k]), float(t.avg_lat[k])]}})
+    return docs
+
+
+def tiles_latest_from_engine(engine, res=None, city="boston", tz=None):
+    """The FeatureCollection api_tiles_latest returns (reference app.py:45-69) for the newest window the engine's
+    state still holds, at H3 resolution res <= the engine's (None: the engine's own): the window's tiles rolled up on
+    the GPU (hm_window_rollup), their boundaries from one more launch (tiles_latest_collection).  "Latest" is the
+    newest window the watermark has not evicted; the reference's Mongo keeps windows until their TTL."""
+    return tiles_latest_collection(tile_docs_from_engine(engine, res, city, tz), engine.device)
+
+
