@@ -28,6 +28,8 @@
  *   hm_encode_position_updates   -- the positions half (:198-235): one positions_latest statement per latest row.
  *   hm_live_windows / hm_window_rollup -- the web API's read of the latest window's tiles (app.py:45-69), from the
  *                                   engine's state instead of MongoDB, at any H3 resolution <= H3_RES.
+ *   hm_positions_*               -- the positions_latest collection itself (:217-228 and app.py:71-88): every vehicle's
+ *                                   newest position so far, folded across batches on the device.
  */
 #ifndef MOBHEAT_H
 #define MOBHEAT_H
@@ -37,7 +39,7 @@
 extern "C" {
 #endif
 
-#define HM_ABI_VERSION 12
+#define HM_ABI_VERSION 13
 
 /* error codes */
 #define HM_OK 0
@@ -464,6 +466,46 @@ int hm_window_rollup(hm_ctx *ctx, int64_t window_start_us, int32_t res, int32_t 
 /* host execution of the kernels' h3_cell_to_parent (no GPU): out[i] = upstream cellToParent(cells[i], res) for
  * res <= the cells' resolution (resolution field := res, digits res+1..15 := 7) */
 int hm_selftest_cell_to_parent(const uint64_t *cells, int64_t n, int32_t res, uint64_t *out);
+
+/* ---- latest position per vehicle across batches (reference heatmap_stream.py:217-228: the positions_latest collection;
+ * app.py:71-88 reads it) ----
+ * An opt-in, device-resident state S: (provider bytes, vehicleId bytes) -> (ts_us, lat, lon).  The two strings are a
+ * pair, not a concatenation; an empty string is a valid part; comparison is byte-exact.  Folding a batch walks its
+ * latest_row in ascending row order: row i of key k replaces S[k] iff k is absent or ts_us[i] > S[k].ts_us (strictly) --
+ * what the collection holds after the reference's statements are applied in order.  lat / lon are the input doubles
+ * bit for bit; folding a batch twice changes nothing; nothing is evicted (the collection has no TTL).
+ * The state is keyed by the strings because a batch's vkey is built from that batch's own dictionaries: the same
+ * vehicle has another vkey in the next batch.  None of these calls touches the tile state or hm_state_version. */
+typedef struct hm_position_rec {
+    uint32_t provider;   /* persistent codes: indices into the dictionaries hm_positions_export returns */
+    uint32_t vehicle;
+    int64_t ts_us;
+    double lat;
+    double lon;
+} hm_position_rec;   /* 32 B */
+/* Folds the last hm_process_batch's latest rows into S.  dicts: the batch's dictionaries, as
+ * hm_encode_position_updates takes them (host memory; the bucket fields are ignored), with that call's preconditions:
+ * the batch's device inputs are still valid; without a processed batch HM_E_STATE.  A latest row whose codes fall
+ * outside the dictionaries, or malformed offsets: HM_E_INVALID, S untouched.  A shard context (shard_count > 1):
+ * HM_E_UNSUPPORTED (the stage API leaves latest rows on the rank that received them).  A batch without latest rows is
+ * a no-op.  A batch that brings no new vehicle allocates nothing. */
+int hm_positions_update(hm_ctx *ctx, const hm_position_doc_cfg *dicts);
+/* S as *n records in no particular order, and the two persistent dictionaries in dicts (Arrow offsets + UTF-8 bytes;
+ * the bucket fields 0).  Library-owned, in device or pinned host memory per out_memory (HM_MEM_DEVICE / HM_MEM_HOST),
+ * valid until the next hm_positions_* call on the context. */
+int hm_positions_export(hm_ctx *ctx, int32_t out_memory, const hm_position_rec **recs, int64_t *n,
+                        hm_position_doc_cfg *dicts);
+/* Restores an export (host memory) into a context whose positions state is empty (HM_E_STATE otherwise).  Duplicate
+ * keys, duplicate dictionary strings, codes outside the dictionaries: HM_E_INVALID. */
+int hm_positions_import(hm_ctx *ctx, const hm_position_rec *recs, int64_t n, const hm_position_doc_cfg *dicts);
+/* up to n of: [0] keys, [1] pair-table capacity (slots), [2] provider strings, [3] vehicle strings, [4] arena bytes in
+ * use (both dictionaries), [5] regrows since create (tables, arenas, code lists), [6] of those: the pair table's,
+ * [7] the vehicle arena's, [8] the last hm_positions_update on the device, microseconds, upload of the dictionaries
+ * included, [9] the same from the first kernel on.  All 0 on a context that never made a positions call. */
+int hm_positions_info(const hm_ctx *ctx, int64_t *v, int32_t n);
+/* Test seam: every string hash is cut to its low `bits` bits (0..64; 64 = off), so that unequal strings with equal
+ * hashes are the common case.  Results stay exact.  Only while the state is empty (HM_E_STATE otherwise). */
+int hm_positions_debug_hash_bits(hm_ctx *ctx, int32_t bits);
 
 /* Counts of the last hm_process_batch / stage batch (up to n of them): [0] keys created in the tile state, [1] partial
  * records merged (direct path: aggregated rows; table mode: ~ distinct keys; stage API: the records this rank

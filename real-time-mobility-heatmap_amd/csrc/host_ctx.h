@@ -138,6 +138,35 @@ struct hm_ctx {
     DevBuf ru_tab, ru_out;
     void *h_ru = nullptr;
     size_t h_ru_cap = 0;
+    // hm_positions_* (api_positions.h, k_positions.h): the latest position per (provider, vehicleId) across batches.
+    // Nothing here is allocated before the first positions call.
+    struct PosDict {   // a persistent string dictionary: table, byte arena, the strings' spans by code
+        PosStr *tab = nullptr;
+        unsigned long long cap = 0;
+        uint8_t *arena = nullptr;
+        size_t arena_cap = 0;
+        unsigned long long *code_off = nullptr;
+        unsigned *code_len = nullptr;
+        size_t codes_cap = 0;
+        int64_t n_codes = 0, arena_used = 0;   // host mirrors of the device words used[1], used[0]
+        int64_t arena_regrows = 0;
+    };
+    struct Positions {
+        bool ready = false;
+        PosDict prov, veh;
+        PosSlot *tab = nullptr;   // cap slots, then cap candidate words
+        unsigned long long cap = 0;
+        int64_t keys = 0;
+        unsigned long long *words = nullptr, *h_words = nullptr;   // PW_WORDS counters | used[2] provider | used[2] vehicle
+        int hash_bits = 64;
+        int64_t regrows = 0, pair_regrows = 0;
+        DevBuf params, p_code, v_code, slot_of, imp;   // a batch's dictionaries and their codes, the rows' slots
+        DevBuf x_recs, x_off[2], x_bytes[2], x_btot, x_boff;   // the export, and its pinned host copy
+        void *h_recs = nullptr, *h_off[2] = {nullptr, nullptr}, *h_bytes[2] = {nullptr, nullptr};
+        size_t h_recs_cap = 0, h_off_cap[2] = {0, 0}, h_bytes_cap[2] = {0, 0};
+        hipEvent_t ev[3] = {};
+        double us[2] = {0, 0};
+    } pos;
     DevBuf keys;                     // k_ingest's event key per row (kernels.h ekey)
     // k_ingest's fused binning (large direct-path batches): the bins' cursors (RP_BINS + 1 u32: the last stays 0, so
     // that their exclusive scan ends with the total) and the slab capacity; the slabs are parts_sorted
@@ -235,6 +264,27 @@ struct hm_ctx {
     DevBuf pl_T;                         // one chunk's records per bin (k_chunk_segments -> k_seg_scan)
     unsigned test_slab_cap = 0;          // MOBHEAT_TEST_SLAB_CAP: slabs of at most this many records (tests: overflow)
 };
+
+// hm_destroy's part for the positions state
+static void positions_free(hm_ctx *ctx) {
+    hm_ctx::Positions &P = ctx->pos;
+    for (hm_ctx::PosDict *d : {&P.prov, &P.veh}) {
+        if (d->tab) (void)hipFree(d->tab);
+        if (d->arena) (void)hipFree(d->arena);
+        if (d->code_off) (void)hipFree(d->code_off);
+        if (d->code_len) (void)hipFree(d->code_len);
+    }
+    if (P.tab) (void)hipFree(P.tab);
+    if (P.words) (void)hipFree(P.words);
+    if (P.h_words) (void)hipHostFree(P.h_words);
+    for (DevBuf *b : {&P.params, &P.p_code, &P.v_code, &P.slot_of, &P.imp, &P.x_recs, &P.x_off[0], &P.x_off[1], &P.x_bytes[0],
+                      &P.x_bytes[1], &P.x_btot, &P.x_boff})
+        if (b->p) (void)hipFree(b->p);
+    for (void *p : {P.h_recs, P.h_off[0], P.h_off[1], P.h_bytes[0], P.h_bytes[1]})
+        if (p) (void)hipHostFree(p);
+    for (auto &e : P.ev)
+        if (e) (void)hipEventDestroy(e);
+}
 
 static std::string g_create_err;
 // rows of one batch (and records of one stage merge): positions are 32-bit, and k_ev_scatter_rec's lanes past a tile

@@ -11,8 +11,9 @@
 //   k_json.h        Kafka values -> columns, string dictionaries
 //   k_stage.h       multi-GPU exchange helpers
 //   k_rollup.h      read side: one window's tiles rolled up to a coarser resolution (k_rollup, k_rollup_emit)
+//   k_positions.h   the latest position per (provider, vehicleId) across batches (k_pos_*)
 //   host_ctx.h      the context, allocation, per-window tables, launchers;  host_batch.h: the batch phases
-//   api_*.h         the C ABI of include/mobheat.h (batch, UDF/read side, stage API, checkpoint, sink, JSON, window reads, self-tests)
+//   api_*.h         the C ABI of include/mobheat.h (batch, UDF/read side, stage API, checkpoint, sink, JSON, window reads, positions, self-tests)
 //
 // Pipeline per batch (one HIP stream per context; every arithmetic step runs on the GPU):
 //   k_ingest      filter (heatmap_stream.py:96-104) + H3 latLngToCell UDF (:65-75,105) + tumbling window (:115) +
@@ -38,7 +39,9 @@
 #include <cstdlib>
 #include <ctime>
 #include <string>
+#include <string_view>
 #include <type_traits>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/mobheat.h"
@@ -79,6 +82,7 @@ static hipError_t upload_tables() {
 #include "k_json.h"
 #include "k_stage.h"
 #include "k_rollup.h"
+#include "k_positions.h"
 #include "host_ctx.h"
 #include "host_batch.h"
 #include "host_pipe.h"
@@ -92,6 +96,7 @@ extern "C" {
 #include "api_sink.h"
 #include "api_json.h"
 #include "api_read.h"
+#include "api_positions.h"
 #include "api_selftest.h"
 
 }  // extern "C"

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # MOBHEAT_LIB: load another build of the same ABI (kernel variants under csrc/variants/ for tuning runs)
 LIB_PATH = os.environ.get("MOBHEAT_LIB") or os.path.normpath(os.path.join(_HERE, "..", "csrc", "libmobheat.so"))
 
-HM_ABI_VERSION = 12
+HM_ABI_VERSION = 13
 HM_MEM_HOST = 0
 HM_MEM_DEVICE = 1
 HM_MEM_HOST_STREAM = 2
@@ -100,6 +100,10 @@ STATE_REC_DTYPE = np.dtype([("cell", "<u8"), ("window_start_us", "<i8"), ("count
                             ("sum_speed", "<f8"), ("sum_lat", "<f8"), ("sum_lon", "<f8"), ("reserved", "<i8")])
 assert STATE_REC_DTYPE.itemsize == 64
 
+# hm_position_rec (32 B): one (provider, vehicleId) key of the positions state, by persistent dictionary codes
+POSITION_REC_DTYPE = np.dtype([("provider", "<u4"), ("vehicle", "<u4"), ("ts_us", "<i8"), ("lat", "<f8"), ("lon", "<f8")])
+assert POSITION_REC_DTYPE.itemsize == 32
+
 _P = ctypes.POINTER
 # name -> (restype, argtypes); must match include/mobheat.h (tests/test_abi.py checks the symbol set)
 SIGNATURES = {
@@ -157,6 +161,11 @@ SIGNATURES = {
     "hm_live_windows": (c_i32, [c_vp, c_vp, c_vp, c_i64, _P(c_i64)]),
     "hm_window_rollup": (c_i32, [c_vp, c_i64, c_i32, c_i32, _P(c_vp), _P(c_i64)]),
     "hm_selftest_cell_to_parent": (c_i32, [c_vp, c_i64, c_i32, c_vp]),
+    "hm_positions_update": (c_i32, [c_vp, _P(HmPositionDocCfg)]),
+    "hm_positions_export": (c_i32, [c_vp, c_i32, _P(c_vp), _P(c_i64), _P(HmPositionDocCfg)]),
+    "hm_positions_import": (c_i32, [c_vp, c_vp, c_i64, _P(HmPositionDocCfg)]),
+    "hm_positions_info": (c_i32, [c_vp, c_vp, c_i32]),
+    "hm_positions_debug_hash_bits": (c_i32, [c_vp, c_i32]),
     "hm_abi_version": (c_i32, []),
 }
 
@@ -356,6 +365,19 @@ def position_doc_cfg(provider_uniques, vehicle_uniques, ts_us, bucket_ids=None):
         cfg.vehicle_offsets = ptr(vo2)
         return cfg, (po, pb, vo, vb, bi, bo, vo2)
     return cfg, (po, pb, vo, vb, bi, bo)
+
+
+def position_dicts_cfg(provider_uniques, vehicle_uniques):
+    """hm_position_doc_cfg holding only the two dictionaries (hm_positions_update / hm_positions_import ignore the
+    buckets): lists of str, Arrow string arrays or (n, offsets, bytes); the returned tuple keeps the arrays alive."""
+    np_, po, pb = provider_uniques if isinstance(provider_uniques, tuple) else _dictionary(provider_uniques)
+    nv, vo, vb = vehicle_uniques if isinstance(vehicle_uniques, tuple) else _dictionary(vehicle_uniques)
+    po, vo = np.ascontiguousarray(po, np.int64), np.ascontiguousarray(vo, np.int64)
+    pb, vb = np.ascontiguousarray(pb, np.uint8), np.ascontiguousarray(vb, np.uint8)
+    cfg = HmPositionDocCfg(n_providers=np_, provider_offsets=ptr(po), provider_bytes=ptr(pb), n_vehicles=nv,
+                           vehicle_offsets=ptr(vo), vehicle_bytes=ptr(vb), n_buckets=0, bucket_ids=None,
+                           bucket_offset_s=None)
+    return cfg, (po, pb, vo, vb)
 
 
 def position_statements_selftest(provider_uniques, vehicle_uniques, vkey, ts_us, lat, lon):

@@ -447,6 +447,56 @@ class HeatmapEngine:
               "hm_encode_position_updates")
         return _host_statements(pb, po, nd, copy)
 
+    # ---- every vehicle's latest position across batches (hm_positions_*; reference heatmap_stream.py:217-228) ----
+    def update_positions(self, provider_uniques, vehicle_uniques=None):
+        """Fold the last batch's latest rows into the engine's positions state: per (provider, vehicleId) string pair
+        the row with the newest eventTs so far (strictly newer replaces; among a batch's tied rows the lowest), what
+        positions_latest holds after the reference's statements.  The dictionaries are the batch's, as
+        encode_position_updates takes them (or one (providers, vehicles) tuple).  Folding a batch twice changes
+        nothing."""
+        if vehicle_uniques is None:
+            provider_uniques, vehicle_uniques = provider_uniques
+        cfg, keep = _lib.position_dicts_cfg(provider_uniques, vehicle_uniques)
+        check(self._lib.hm_positions_update(self._ctx, ctypes.byref(cfg)), self._ctx, "hm_positions_update")
+
+    def positions(self, strings=True):
+        """The positions state: (records POSITION_REC_DTYPE in no particular order, providers, vehicles) -- the
+        record's provider / vehicle index the two lists (str; strings=False: (n, offsets int64, bytes uint8))."""
+        p, n, cfg = ctypes.c_void_p(), ctypes.c_int64(), _lib.HmPositionDocCfg()
+        check(self._lib.hm_positions_export(self._ctx, HM_MEM_HOST, ctypes.byref(p), ctypes.byref(n), ctypes.byref(cfg)),
+              self._ctx, "hm_positions_export")
+        if n.value:
+            raw = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)),
+                                        shape=(n.value * _lib.POSITION_REC_DTYPE.itemsize,))
+            recs = raw.view(_lib.POSITION_REC_DTYPE).copy()
+        else:
+            recs = np.zeros(0, _lib.POSITION_REC_DTYPE)
+
+        def dictionary(m, po, pb):
+            offs = np.ctypeslib.as_array(ctypes.cast(po, ctypes.POINTER(ctypes.c_int64)), shape=(m + 1,)).copy()
+            total = int(offs[-1])
+            raw = (np.ctypeslib.as_array(ctypes.cast(pb, ctypes.POINTER(ctypes.c_uint8)), shape=(total,)).copy()
+                   if total else np.zeros(1, np.uint8))
+            if not strings:
+                return m, offs, raw
+            b = raw.tobytes()
+            return [b[offs[k]:offs[k + 1]].decode("utf-8") for k in range(m)]
+        return (recs, dictionary(int(cfg.n_providers), cfg.provider_offsets, cfg.provider_bytes),
+                dictionary(int(cfg.n_vehicles), cfg.vehicle_offsets, cfg.vehicle_bytes))
+
+    def import_positions(self, recs, providers, vehicles):
+        """Restore positions() into an engine whose positions state is empty."""
+        recs = np.ascontiguousarray(recs, dtype=_lib.POSITION_REC_DTYPE)
+        cfg, keep = _lib.position_dicts_cfg(providers, vehicles)
+        check(self._lib.hm_positions_import(self._ctx, ptr(recs) if recs.size else None, recs.size, ctypes.byref(cfg)),
+              self._ctx, "hm_positions_import")
+
+    def positions_info(self):
+        v = (ctypes.c_int64 * 10)()
+        check(self._lib.hm_positions_info(self._ctx, v, 10), self._ctx, "hm_positions_info")
+        return {"keys": v[0], "capacity": v[1], "providers": v[2], "vehicles": v[3], "arena_bytes": v[4], "regrows": v[5],
+                "pair_regrows": v[6], "vehicle_arena_regrows": v[7], "update_us": v[8], "update_kernels_us": v[9]}
+
     def encode_tile_updates_device(self, city, ttl_minutes):
         """The same, left on the device: (device pointer of the bytes, of the offsets, n statements)."""
         n = ctypes.c_int64()

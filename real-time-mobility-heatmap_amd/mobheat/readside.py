@@ -95,3 +95,40 @@ def tiles_latest_from_engine(engine, res=None, city="boston", tz=None):
     return tiles_latest_collection(tile_docs_from_engine(engine, res, city, tz), engine.device)
 
 
+def positions_latest_collection(docs):
+    """The FeatureCollection of reference app.py:71-88 for documents shaped like the positions_latest collection
+    (provider, vehicleId, ts, loc: {type: Point, coordinates: [lon, lat]})."""
+    import datetime as _dt
+    features = []
+    for d in docs:
+        lon, lat = d["loc"]["coordinates"]
+        ts = d.get("ts")
+        props = {"provider": d.get("provider"), "vehicleId": d.get("vehicleId"),
+                 "ts": ts.isoformat() if isinstance(ts, _dt.datetime) else str(ts)}
+        features.append({"type": "Feature", "geometry": {"type": "Point", "coordinates": [lon, lat]}, "properties": props})
+    return {"type": "FeatureCollection", "features": features}
+
+
+def position_docs_from_engine(engine, tz=None):
+    """The engine's positions state (HeatmapEngine.positions) as positions_latest documents: _id "provider|vehicleId",
+    provider, vehicleId, ts (the naive local datetime the sink writes, or zone tz's wall time: tile_docs_from_engine's
+    convention), loc."""
+    import datetime as _dt
+
+    from .stream import _spark_datetime
+    recs, providers, vehicles = engine.positions()
+    docs = []
+    for r in recs:
+        us = int(r["ts_us"])
+        ts = (_spark_datetime(us) if tz is None else
+              _dt.datetime.fromtimestamp(us // 1000000, tz).replace(tzinfo=None, microsecond=us % 1000000))
+        p, v = providers[int(r["provider"])], vehicles[int(r["vehicle"])]
+        docs.append({"_id": f"{p}|{v}", "provider": p, "vehicleId": v, "ts": ts,
+                     "loc": {"type": "Point", "coordinates": [float(r["lon"]), float(r["lat"])]}})
+    return docs
+
+
+def positions_latest_from_engine(engine, tz=None):
+    """The FeatureCollection api_positions_latest returns (reference app.py:71-88), from the engine's positions state
+    (HeatmapEngine.update_positions after each batch) -- no MongoDB in between."""
+    return positions_latest_collection(position_docs_from_engine(engine, tz))

@@ -46,6 +46,16 @@ DIST_BACKEND = os.getenv("MOBHEAT_DIST_BACKEND", "nccl")
 # one-GPU machine)
 FORCE_SHARDED = os.getenv("MOBHEAT_SHARDED", "0") == "1"
 STATE_CHECKPOINT = os.getenv("MOBHEAT_STATE_CHECKPOINT", "1") == "1"
+# MOBHEAT_POSITIONS=1: after each batch the engine folds the batch's latest rows into its positions state
+# (HeatmapEngine.update_positions: every vehicle's newest position so far, what positions_latest holds), which
+# readside.positions_latest_from_engine serves without MongoDB.  Single-engine path only; read per batch.
+_POSITIONS_NOTE = [False]
+
+
+def positions_enabled():
+    return os.getenv("MOBHEAT_POSITIONS", "0") == "1"
+
+
 STATE_FULL_EVERY = int(os.getenv("MOBHEAT_STATE_FULL_EVERY", "10"))
 # The engine's window tables are carved from a zeroed reservation made at its creation (hm_config.state_arena_bytes)
 # before any allocation inside a batch: "auto" sizes it from the first batch the process sees (ARENA_BYTES_PER_ROW per
@@ -784,6 +794,10 @@ def _foreach_sharded(df, epoch):
     that epoch on the state before it).  Replay and failure semantics as the single-GPU path."""
     global _LAST_EPOCH, _PENDING
     from .engine import BatchResult
+    if positions_enabled() and not _POSITIONS_NOTE[0]:
+        import warnings
+        _POSITIONS_NOTE[0] = True   # (once: every rank holds only the latest rows it received, so there is no fold here)
+        warnings.warn("mobheat: MOBHEAT_POSITIONS=1 is ignored by the sharded writer (the positions state is single-engine)")
     sh = get_sharded()
     if _PENDING is not None and _PENDING[0] == epoch and sh.last is not None:
         per_rank = sh.last   # the replay of the epoch whose writes failed: every rank's state is in place
@@ -904,6 +918,11 @@ def foreach_batch_func(df, epoch_id: int):
             lap("encode")
             _flush_statements(sink, "positions_latest", buf, offs, landed)
             lap("sink")
+            # (after the statements: the fold shares nothing with them; a replay of this epoch folds again, which
+            # changes nothing)
+            if positions_enabled():
+                eng.update_positions(*dicts)
+                lap("positions")
     finally:
         sink.close()
         if ckpt is not None:   # (also when a write failed: a replay must not race the file)
