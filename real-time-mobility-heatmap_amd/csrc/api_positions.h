@@ -129,6 +129,13 @@ static int pos_pairs_grow(hm_ctx *ctx, int64_t need_keys) {
     return HM_OK;
 }
 static unsigned *pos_cand(const hm_ctx::Positions &P) { return (unsigned *)(P.tab + P.cap); }
+// the end of a call that counted into the control block (copied to h_words): HM_E_OVERFLOW if a probe bound ran out
+static int pos_overflow_status(hm_ctx *ctx) {
+    const unsigned long long lost = ctx->pos.h_words[PW_OVERFLOW];
+    if (!lost) return HM_OK;
+    return set_err(ctx, HM_E_OVERFLOW, "positions tables: %llu probes past the bound of %llu (colliding string hashes)", lost,
+                   POS_PROBES);
+}
 
 // host-side shape of a caller's dictionaries (the offsets themselves are checked where they are read: on the device
 // for a batch's, on the host for an import's)
@@ -233,10 +240,7 @@ int hm_positions_update(hm_ctx *ctx, const hm_position_doc_cfg *dicts) {
     P.prov.n_codes = (int64_t)P.h_words[POS_USED_P + 1];
     P.veh.arena_used = (int64_t)P.h_words[POS_USED_V];
     P.veh.n_codes = (int64_t)P.h_words[POS_USED_V + 1];
-    if (P.h_words[PW_OVERFLOW])
-        return set_err(ctx, HM_E_OVERFLOW, "positions tables: %llu probes past the bound of %llu (colliding string hashes)",
-                       P.h_words[PW_OVERFLOW], POS_PROBES);
-    return HM_OK;
+    return pos_overflow_status(ctx);
 }
 
 // exclusive scan of a dictionary's code lengths into Arrow offsets (n + 1 entries; the total is its arena's fill)
@@ -387,10 +391,7 @@ int hm_positions_import(hm_ctx *ctx, const hm_position_rec *recs, int64_t n, con
     P.veh.n_codes = nv;
     P.veh.arena_used = v_total;
     P.keys = n;
-    if (P.h_words[PW_OVERFLOW])
-        return set_err(ctx, HM_E_OVERFLOW, "positions tables: %llu probes past the bound of %llu (colliding string hashes)",
-                       P.h_words[PW_OVERFLOW], POS_PROBES);
-    return HM_OK;
+    return pos_overflow_status(ctx);
 }
 
 int hm_positions_info(const hm_ctx *ctx, int64_t *v, int32_t n) {

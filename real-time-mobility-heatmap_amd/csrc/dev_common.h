@@ -12,6 +12,17 @@ __device__ __forceinline__ T wave_sum(T v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// inclusive prefix of v over the wave's 64 lanes, in lane order (lane 63 holds the wave's sum)
+template <typename T>
+__device__ __forceinline__ T wave_inclusive_scan(T v) {
+    const int ln = lane_id();
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_up(v, o, 64);
+        if (ln >= o) v += y;
+    }
+    return v;
+}
 __device__ __forceinline__ long long wave_max(long long v) {
     for (int o = 32; o > 0; o >>= 1) { long long w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
     return v;
@@ -21,12 +32,7 @@ __device__ __forceinline__ long long wave_max(long long v) {
 __device__ __forceinline__ unsigned long long block1024_exclusive(unsigned long long v, unsigned long long *total) {
     __shared__ unsigned long long wtot[16];
     const int ln = lane_id(), w = threadIdx.x >> 6;
-    unsigned long long x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long y = __shfl_up(x, o, 64);
-        if (ln >= o) x += y;
-    }
+    const unsigned long long x = wave_inclusive_scan(v);
     if (ln == 63) wtot[w] = x;
     __syncthreads();
     if (w == 0) {
@@ -199,12 +205,7 @@ __device__ __forceinline__ bool wave_count_windows(bool pred, unsigned long long
         int leader = __ffsll((long long)pend) - 1;
         unsigned long long wl = __shfl(we, leader, 64);
         bool match = pred && we == wl;
-        unsigned long long sum = 0;
-        {
-            unsigned long long v = match ? c : 0;
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-            sum = v;
-        }
+        const unsigned long long sum = wave_sum(match ? c : 0ull);
         if (lane_id() == leader) ok = wl_add(L, g, wl, sum);
         pred = pred && !match;
     }

@@ -25,62 +25,33 @@ __global__ __launch_bounds__(256) void k_census(const TilePartial *__restrict__ 
 // merged into its new table by k_merge_owned in rehash mode
 // (only_seq != 0: only the keys whose touched word carries that batch sequence -- an incremental checkpoint)
 // (clear_touched: a checkpoint export -- the touched word means nothing outside this context)
-// Each workgroup iteration reads DUMP_PER x 256 consecutive slots (coalesced: slot k * 256 + tid) and appends its live
-// keys with ONE atomic on the shared counter: a wave-aggregated append still made one same-address atomic per wave --
-// 1.5 M of them over three 2^25-slot windows serialised at the L2 (12.7 ms for a 1e7-key delta, profiles/r6/r6w2);
-// the record order in `out` is irrelevant to every caller (growth re-partitions, checkpoints are key sets).
-constexpr int DUMP_PER = 8;
+// compacted by block256_compact (dev_table.h): the record order in `out` is irrelevant to every caller
 __global__ __launch_bounds__(256) void k_dump_gen(GenDesc g, GrowRec *__restrict__ out, unsigned long long *n_out,
                                                   unsigned only_seq = 0, bool clear_touched = false) {
-    __shared__ unsigned wave_n[4];
-    __shared__ unsigned long long blk_base;
     const int64_t cap = (int64_t)((g.rmask + 1) << g.rbits);
     const int64_t tile = 256 * DUMP_PER;
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const unsigned long long below = (UINT64_C(1) << lane) - 1;
     for (int64_t base = (int64_t)blockIdx.x * tile; base < cap; base += (int64_t)gridDim.x * tile) {
-        bool live[DUMP_PER];
-        unsigned long long m[DUMP_PER];
-        unsigned wtot = 0;
-#pragma unroll
-        for (int k = 0; k < DUMP_PER; k++) {
-            const int64_t i = base + k * 256 + threadIdx.x;
-            live[k] = false;
+        const auto is_live = [=, &g](int64_t i) {   // (g: the descriptor in the kernel's arguments, not copied)
+            bool live = false;
             if (i < cap) {
                 const unsigned long long we = g.tab[i].wenc;
-                live[k] = we == g.wenc && (only_seq == 0 || (unsigned)(g.tab[i].touched >> 32) == only_seq);
+                live = we == g.wenc && (only_seq == 0 || (unsigned)(g.tab[i].touched >> 32) == only_seq);
             }
-            m[k] = __ballot(live[k]);
-            wtot += __popcll(m[k]);
-        }
-        // the wave's k-th records go after its records of earlier k, in lane order
-        if (lane == 0) wave_n[wave] = wtot;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned tot = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
-            blk_base = tot ? atomicAdd(n_out, (unsigned long long)tot) : 0ull;
-        }
-        __syncthreads();
-        unsigned long long pos = blk_base;
-        for (int w = 0; w < wave; w++) pos += wave_n[w];
-#pragma unroll
-        for (int k = 0; k < DUMP_PER; k++) {
-            if (live[k]) {
-                const TileSlot sl = g.tab[base + k * 256 + threadIdx.x];
-                GrowRec p;
-                p.cell = sl.cell;
-                p.wstart = wdec(sl.wenc);
-                p.count = sl.count;
-                p.nspeed = sl.nspeed;
-                p.sspeed = sl.sspeed;
-                p.slat = sl.slat;
-                p.slon = sl.slon;
-                p.touched = clear_touched ? 0ull : sl.touched;
-                out[pos + __popcll(m[k] & below)] = p;
-            }
-            pos += __popcll(m[k]);
-        }
-        __syncthreads();   // (wave_n / blk_base reused by the next iteration)
+            return live;
+        };
+        block256_compact<false>(base, is_live, n_out, 0, [=, &g](int64_t i, unsigned long long at) {
+            const TileSlot sl = g.tab[i];
+            GrowRec p;
+            p.cell = sl.cell;
+            p.wstart = wdec(sl.wenc);
+            p.count = sl.count;
+            p.nspeed = sl.nspeed;
+            p.sspeed = sl.sspeed;
+            p.slat = sl.slat;
+            p.slon = sl.slon;
+            p.touched = clear_touched ? 0ull : sl.touched;
+            out[at] = p;
+        });
     }
 }
 

@@ -6,7 +6,9 @@
 // =====================================================================================================
 // A batch's vkey is provider_code * n_vehicles + vehicle_code of that batch's own dictionaries, so the state is keyed by
 // the strings themselves.  Three tables, all open addressing with linear probing, load <= 1/2, sized by the host before
-// the launch for everything the batch can bring (no kernel can run out of slots or arena mid-flight):
+// the launch for everything the batch can bring (no kernel can run out of slots or arena mid-flight).  Every claim and
+// the pair table's lookups go through tab_probe (dev_table.h), bounded by POS_PROBES; the export's compaction is
+// block256_compact (dev_table.h):
 //  string dictionaries  one for provider, one for vehicleId.  A slot (PosStr, 24 B, cleared to all-ones bytes) holds the
 //                    string's 63-bit hash, its span in an append-only byte arena and its persistent code (dense, in
 //                    order of insertion; never reused).  code_off / code_len list the spans by code (the export).
@@ -62,6 +64,18 @@ __device__ __forceinline__ bool pos_bytes_equal(const uint8_t *a, const uint8_t 
     for (int k = 0; k < n; k++)
         if (a[k] != b[k]) return false;
     return true;
+}
+// the key words of a positions table (PosStr or PosSlot), as tab_probe (dev_table.h) reaches them
+template <class Slot>
+__device__ __forceinline__ auto pos_keys(Slot *tab) {
+    return [tab](unsigned long long i) { return &tab[i].key; };
+}
+// claims the first free slot of `key`'s probe chain and compares nothing: the caller guarantees distinct keys, none of
+// them in the table.  TAB_NONE: no free slot within the probe bound (the caller counts it in words[PW_OVERFLOW]).
+template <class Slot>
+__device__ __forceinline__ unsigned long long pos_claim(Slot *tab, unsigned long long mask, unsigned long long key) {
+    unsigned long long seen;
+    return tab_probe<true>(pos_keys(tab), mask, mix64(key) & mask, POS_PROBES, POS_EMPTY, key, TabNoMatch{}, seen);
 }
 
 // words of the control block (device; zeroed before every call that counts into them)
@@ -137,28 +151,13 @@ __global__ __launch_bounds__(256) void k_pos_str_insert(const int64_t *__restric
         const bool mine = k < n && code_of[k] == POS_NONE;
         const uint8_t *s = mine ? bytes + off[k] : nullptr;
         const unsigned len = mine ? (unsigned)(off[k + 1] - off[k]) : 0u;
-        unsigned long long slot = POS_EMPTY;
-        if (mine) {
-            const unsigned long long h = pos_hash(s, (int)len, bits);
-            unsigned long long at = mix64(h) & mask;
-            for (unsigned long long q = 0; q < POS_PROBES && q <= mask; q++) {
-                // (a stale read can only be EMPTY, and the CAS then returns the slot's owner; an owner of this launch
-                // is another string by the invariant, an older one was compared by k_pos_str_find: probe on)
-                unsigned long long cur = __hip_atomic_load(&tab[at].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (cur == POS_EMPTY) cur = atomicCAS(&tab[at].key, POS_EMPTY, h);
-                if (cur == POS_EMPTY) { slot = at; break; }
-                at = (at + 1) & mask;
-            }
-        }
-        const bool won = slot != POS_EMPTY;
+        // (claim only: a slot's owner of this launch is another string by the invariant, an older one was compared by
+        // k_pos_str_find: probe on)
+        const unsigned long long slot = mine ? pos_claim(tab, mask, pos_hash(s, (int)len, bits)) : TAB_NONE;
+        const bool won = slot != TAB_NONE;
         // this wave's reservation: bytes and codes, one atomic each
         const unsigned long long m = __ballot(won);
-        unsigned long long pre = won ? len : 0u;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long y = __shfl_up(pre, o, 64);
-            if (ln >= o) pre += y;
-        }
+        const unsigned long long pre = wave_inclusive_scan<unsigned long long>(won ? len : 0u);
         const unsigned long long tot = __shfl(pre, 63, 64);
         unsigned long long b0 = 0, c0 = 0;
         if (m) {
@@ -193,15 +192,8 @@ __global__ __launch_bounds__(256) void k_pos_str_import(const int64_t *__restric
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
         const unsigned len = (unsigned)(off[k + 1] - off[k]);
-        const unsigned long long h = pos_hash(arena + off[k], (int)len, bits);
-        unsigned long long at = mix64(h) & mask, slot = POS_EMPTY;
-        for (unsigned long long q = 0; q < POS_PROBES && q <= mask; q++) {
-            unsigned long long cur = __hip_atomic_load(&tab[at].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == POS_EMPTY) cur = atomicCAS(&tab[at].key, POS_EMPTY, h);
-            if (cur == POS_EMPTY) { slot = at; break; }
-            at = (at + 1) & mask;
-        }
-        if (slot == POS_EMPTY) { atomicAdd(&words[PW_OVERFLOW], 1ull); continue; }
+        const unsigned long long slot = pos_claim(tab, mask, pos_hash(arena + off[k], (int)len, bits));
+        if (slot == TAB_NONE) { atomicAdd(&words[PW_OVERFLOW], 1ull); continue; }
         tab[slot].off = (unsigned long long)off[k];
         tab[slot].len = len;
         tab[slot].code = (unsigned)k;
@@ -217,43 +209,25 @@ __global__ __launch_bounds__(256) void k_pos_str_rehash(const PosStr *__restrict
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < old_cap; i += stride) {
         const PosStr e = old[i];
         if (e.key == POS_EMPTY) continue;
-        unsigned long long at = mix64(e.key) & mask, slot = POS_EMPTY;
-        for (unsigned long long q = 0; q < POS_PROBES && q <= mask; q++) {
-            unsigned long long cur = __hip_atomic_load(&tab[at].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == POS_EMPTY) cur = atomicCAS(&tab[at].key, POS_EMPTY, e.key);
-            if (cur == POS_EMPTY) { slot = at; break; }
-            at = (at + 1) & mask;
-        }
-        if (slot == POS_EMPTY) { atomicAdd(&words[PW_OVERFLOW], 1ull); continue; }
+        const unsigned long long slot = pos_claim(tab, mask, e.key);
+        if (slot == TAB_NONE) { atomicAdd(&words[PW_OVERFLOW], 1ull); continue; }
         tab[slot].off = e.off;
         tab[slot].len = e.len;
         tab[slot].code = e.code;
     }
 }
 
-// the slot of pair key `key` (< 2^63), claimed with POS_FRESH if absent; POS_EMPTY: the probe bound ran out.
-// fresh: the slot was claimed during this launch (by this thread or another).
+// the slot of pair key `key` (< 2^63), claimed with POS_FRESH if absent; TAB_NONE: the probe bound ran out.
+// claimed: by this thread; fresh: the slot was claimed during this launch (by this thread or another).
 __device__ __forceinline__ unsigned long long pos_pair_slot(PosSlot *tab, unsigned long long mask, unsigned long long key,
                                                             bool &fresh, bool &claimed) {
-    unsigned long long at = mix64(key) & mask;
-    claimed = false;
-    for (unsigned long long q = 0; q < POS_PROBES && q <= mask; q++) {
-        // (a stale read can only be EMPTY, and the CAS then returns the slot's owner)
-        unsigned long long cur = __hip_atomic_load(&tab[at].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == POS_EMPTY) {
-            cur = atomicCAS(&tab[at].key, POS_EMPTY, key | POS_FRESH);
-            if (cur == POS_EMPTY) {
-                fresh = claimed = true;
-                return at;
-            }
-        }
-        if ((cur & ~POS_FRESH) == key) {   // (cur != POS_EMPTY here: a key's codes stay below POS_MAX_CODES)
-            fresh = (cur & POS_FRESH) != 0;
-            return at;
-        }
-        at = (at + 1) & mask;
-    }
-    return POS_EMPTY;
+    // (an occupied slot's word is never POS_EMPTY with POS_FRESH ignored: a key's codes stay below POS_MAX_CODES)
+    unsigned long long seen = 0;
+    const unsigned long long at = tab_probe<true>(pos_keys(tab), mask, mix64(key) & mask, POS_PROBES, POS_EMPTY, key | POS_FRESH,
+                                                  TabKeyIs{key, POS_FRESH}, seen);
+    claimed = seen == POS_EMPTY;
+    fresh = (seen & POS_FRESH) != 0;   // (POS_EMPTY has the bit too)
+    return at;
 }
 
 // read only, ahead of a fold whose worst case (every row a new pair) would not fit the table: the latest rows whose pair
@@ -272,13 +246,9 @@ __global__ __launch_bounds__(256) void k_pos_pair_count(const int64_t *__restric
         bool found = false;
         if (tab && pc != POS_NONE && vc != POS_NONE) {
             const unsigned long long key = ((unsigned long long)pc << 32) | vc;
-            unsigned long long at = mix64(key) & mask;
-            for (unsigned long long t = 0; t < POS_PROBES && t <= mask; t++) {
-                const unsigned long long cur = tab[at].key;   // (written by earlier launches: no POS_FRESH, no race)
-                if (cur == POS_EMPTY) break;
-                if (cur == key) { found = true; break; }
-                at = (at + 1) & mask;
-            }
+            unsigned long long seen;   // (the table was written by earlier launches: no POS_FRESH, no race)
+            found = tab_probe<false>(pos_keys(tab), mask, mix64(key) & mask, POS_PROBES, POS_EMPTY, 0ull, TabKeyIs{key, 0ull},
+                                     seen) != TAB_NONE;
         }
         absent += !found;
     }
@@ -302,9 +272,9 @@ __global__ __launch_bounds__(256) void k_pos_pair_pass1(const int64_t *__restric
         const unsigned long long key = ((unsigned long long)pc << 32) | vc;
         bool fresh = false, claimed = false;
         // (a string k_pos_str_insert found no slot for has no code: its rows are lost, and counted)
-        const unsigned long long s = pc == POS_NONE || vc == POS_NONE ? POS_EMPTY : pos_pair_slot(tab, mask, key, fresh, claimed);
-        slot_of[q] = s == POS_EMPTY ? POS_NONE : (unsigned)s;
-        if (s == POS_EMPTY) { lost++; continue; }
+        const unsigned long long s = pc == POS_NONE || vc == POS_NONE ? TAB_NONE : pos_pair_slot(tab, mask, key, fresh, claimed);
+        slot_of[q] = s == TAB_NONE ? POS_NONE : (unsigned)s;
+        if (s == TAB_NONE) { lost++; continue; }
         created += claimed;
         // (a slot that is not fresh holds the ts an earlier fold wrote: nothing writes ts during this launch)
         if (fresh || ts[r] > tab[s].ts) atomicMin(&cand[s], (unsigned)r);
@@ -344,66 +314,32 @@ __global__ __launch_bounds__(256) void k_pos_pair_put(const PosSlot *__restrict_
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const PosSlot e = src[i];
         if (e.key == POS_EMPTY) continue;
-        unsigned long long at = mix64(e.key) & mask, slot = POS_EMPTY;
-        for (unsigned long long q = 0; q < POS_PROBES && q <= mask; q++) {
-            unsigned long long cur = __hip_atomic_load(&tab[at].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == POS_EMPTY) cur = atomicCAS(&tab[at].key, POS_EMPTY, e.key);
-            if (cur == POS_EMPTY) { slot = at; break; }
-            at = (at + 1) & mask;
-        }
-        if (slot == POS_EMPTY) { atomicAdd(&words[PW_OVERFLOW], 1ull); continue; }
+        const unsigned long long slot = pos_claim(tab, mask, e.key);
+        if (slot == TAB_NONE) { atomicAdd(&words[PW_OVERFLOW], 1ull); continue; }
         tab[slot].ts = e.ts;
         tab[slot].lat = e.lat;
         tab[slot].lon = e.lon;
     }
 }
 
-// export: the occupied slots as hm_position_rec, compacted (one counter atomic per workgroup iteration, as
-// k_rollup_emit); records past out_cap are counted, not written
+// export: the occupied slots as hm_position_rec, compacted by block256_compact (dev_table.h); records past out_cap are
+// counted, not written
 __global__ __launch_bounds__(256) void k_pos_emit(const PosSlot *__restrict__ tab, int64_t nslots,
                                                   hm_position_rec *__restrict__ out, int64_t out_cap,
                                                   unsigned long long *n_out) {
-    __shared__ unsigned wave_n[4];
-    __shared__ unsigned long long blk_base;
     const int64_t tile = 256 * DUMP_PER;
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const unsigned long long below = (UINT64_C(1) << lane) - 1;
     for (int64_t base = (int64_t)blockIdx.x * tile; base < nslots; base += (int64_t)gridDim.x * tile) {
-        bool live[DUMP_PER];
-        unsigned long long m[DUMP_PER];
-        unsigned wtot = 0;
-#pragma unroll
-        for (int k = 0; k < DUMP_PER; k++) {
-            const int64_t i = base + k * 256 + threadIdx.x;
-            live[k] = i < nslots && tab[i].key != POS_EMPTY;
-            m[k] = __ballot(live[k]);
-            wtot += __popcll(m[k]);
-        }
-        if (lane == 0) wave_n[wave] = wtot;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned tot = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
-            blk_base = tot ? atomicAdd(n_out, (unsigned long long)tot) : 0ull;
-        }
-        __syncthreads();
-        unsigned long long pos = blk_base;
-        for (int w = 0; w < wave; w++) pos += wave_n[w];
-#pragma unroll
-        for (int k = 0; k < DUMP_PER; k++) {
-            const unsigned long long at = pos + __popcll(m[k] & below);
-            if (live[k] && at < (unsigned long long)out_cap) {
-                const PosSlot e = tab[base + k * 256 + threadIdx.x];
-                hm_position_rec r;
-                r.provider = (uint32_t)(e.key >> 32);
-                r.vehicle = (uint32_t)e.key;
-                r.ts_us = e.ts;
-                r.lat = e.lat;
-                r.lon = e.lon;
-                out[at] = r;
-            }
-            pos += __popcll(m[k]);
-        }
-        __syncthreads();   // (wave_n / blk_base reused by the next iteration)
+        const auto is_live = [=](int64_t i) { return i < nslots && tab[i].key != POS_EMPTY; };
+        block256_compact<true>(base, is_live, n_out, (unsigned long long)out_cap, [=](int64_t i, unsigned long long at) {
+            const PosSlot e = tab[i];
+            hm_position_rec r;
+            r.provider = (uint32_t)(e.key >> 32);
+            r.vehicle = (uint32_t)e.key;
+            r.ts_us = e.ts;
+            r.lat = e.lat;
+            r.lon = e.lon;
+            out[at] = r;
+        });
     }
 }
 // export: a persistent dictionary's bytes in code order (offs: the exclusive scan of code_len)

@@ -20,9 +20,10 @@ HM_HD uint64_t h3_cell_to_parent(uint64_t cell, int r) {
 //                    probe bound) goes to the global table directly: exact, just not pre-aggregated.  Nothing is
 //                    evicted, so a key is never behind an empty slot of its probe chain.
 //  global table      2^k >= 2 * (distinct parents possible) slots of 64 B (a GrowRec each, zeroed before the launch):
-//                    a slot is claimed by a 64-bit CAS on its cell word (0 = free), linear probing wraps over the whole
-//                    table (load <= 1/2: it always ends), counts added with u64 atomics, sums with fp64 atomic adds.
-// k_rollup_emit compacts the claimed slots into hm_state_rec records.
+//                    a slot is found or claimed by tab_probe (dev_table.h: a 64-bit CAS on its cell word, 0 = free),
+//                    linear probing wraps over the whole table (load <= 1/2: it always ends), counts added with u64
+//                    atomics, sums with fp64 atomic adds.
+// k_rollup_emit compacts the claimed slots into hm_state_rec records (block256_compact, dev_table.h).
 // =====================================================================================================
 constexpr int RU_THREADS = 1024;
 constexpr int RU_SLOTS = 2048;           // 48 B each: 96 KB of LDS
@@ -68,29 +69,22 @@ __device__ __forceinline__ bool ru_lds_add(RuTable &T, uint64_t p, unsigned long
 // (cannot happen at load <= 1/2; the bound keeps a mis-sized table from spinning)
 __device__ __forceinline__ bool ru_global_add(GrowRec *tab, unsigned long long mask, uint64_t p, unsigned long long c,
                                               unsigned long long ns, double ssp, double sla, double slo) {
-    unsigned long long h = mix64(p) & mask;
-    for (unsigned long long q = 0; q <= mask; q++) {
-        unsigned long long *kp = (unsigned long long *)&tab[h].cell;
-        // (a stale read can only be 0, and the CAS then returns the slot's owner)
-        unsigned long long cur = __hip_atomic_load(kp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == 0) cur = atomicCAS(kp, 0ull, (unsigned long long)p);
-        if (cur == 0 || cur == p) {
-            GrowRec &s = tab[h];
-            atomicAdd((unsigned long long *)&s.count, c);
-            if (ns) {
-                atomicAdd((unsigned long long *)&s.nspeed, ns);
-                atomicAdd(&s.sspeed, ssp);
-            }
-            atomicAdd(&s.slat, sla);
-            atomicAdd(&s.slon, slo);
-            return true;
-        }
-        h = (h + 1) & mask;
+    unsigned long long seen;
+    const unsigned long long h = tab_probe<true>([tab](unsigned long long i) { return (unsigned long long *)&tab[i].cell; }, mask,
+                                                 mix64(p) & mask, mask + 1, 0ull, p, TabKeyIs{p, 0ull}, seen);
+    if (h == TAB_NONE) return false;
+    GrowRec &s = tab[h];
+    atomicAdd((unsigned long long *)&s.count, c);
+    if (ns) {
+        atomicAdd((unsigned long long *)&s.nspeed, ns);
+        atomicAdd(&s.sspeed, ssp);
     }
-    return false;
+    atomicAdd(&s.slat, sla);
+    atomicAdd(&s.slon, slo);
+    return true;
 }
 
-// scans window g's table as k_dump_gen does (DUMP_PER x RU_THREADS consecutive slots per workgroup iteration, slot
+// scans window g's table in tiles of DUMP_PER x RU_THREADS consecutive slots per workgroup iteration (coalesced: slot
 // k * RU_THREADS + tid); a slot is live iff its window word is g's (tables are reused without clearing)
 __global__ __launch_bounds__(RU_THREADS) void k_rollup(GenDesc g, int res, GrowRec *__restrict__ tab, unsigned long long mask,
                                                        unsigned long long *overflow) {
@@ -130,46 +124,18 @@ __global__ __launch_bounds__(RU_THREADS) void k_rollup(GenDesc g, int res, GrowR
     if (__ballot(!ok) && lane_id() == 0) atomicAdd(overflow, 1ull);
 }
 
-// the claimed slots of the global table as records of window wstart (one counter atomic per workgroup iteration, as
-// k_dump_gen); records past out_cap are counted, not written (the host then fails the call)
+// the claimed slots of the global table as records of window wstart, compacted by block256_compact (dev_table.h);
+// records past out_cap are counted, not written (the host then fails the call)
 __global__ __launch_bounds__(256) void k_rollup_emit(const GrowRec *__restrict__ tab, int64_t nslots, int64_t wstart,
                                                      GrowRec *__restrict__ out, int64_t out_cap, unsigned long long *n_out) {
-    __shared__ unsigned wave_n[4];
-    __shared__ unsigned long long blk_base;
     const int64_t tile = 256 * DUMP_PER;
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const unsigned long long below = (UINT64_C(1) << lane) - 1;
     for (int64_t base = (int64_t)blockIdx.x * tile; base < nslots; base += (int64_t)gridDim.x * tile) {
-        bool live[DUMP_PER];
-        unsigned long long m[DUMP_PER];
-        unsigned wtot = 0;
-#pragma unroll
-        for (int k = 0; k < DUMP_PER; k++) {
-            const int64_t i = base + k * 256 + threadIdx.x;
-            live[k] = i < nslots && tab[i].cell != 0;
-            m[k] = __ballot(live[k]);
-            wtot += __popcll(m[k]);
-        }
-        if (lane == 0) wave_n[wave] = wtot;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned tot = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
-            blk_base = tot ? atomicAdd(n_out, (unsigned long long)tot) : 0ull;
-        }
-        __syncthreads();
-        unsigned long long pos = blk_base;
-        for (int w = 0; w < wave; w++) pos += wave_n[w];
-#pragma unroll
-        for (int k = 0; k < DUMP_PER; k++) {
-            const unsigned long long at = pos + __popcll(m[k] & below);
-            if (live[k] && at < (unsigned long long)out_cap) {
-                GrowRec p = tab[base + k * 256 + threadIdx.x];
-                p.wstart = wstart;
-                p.touched = 0;
-                out[at] = p;
-            }
-            pos += __popcll(m[k]);
-        }
-        __syncthreads();   // (wave_n / blk_base reused by the next iteration)
+        const auto is_live = [=](int64_t i) { return i < nslots && tab[i].cell != 0; };
+        block256_compact<true>(base, is_live, n_out, (unsigned long long)out_cap, [=](int64_t i, unsigned long long at) {
+            GrowRec p = tab[i];
+            p.wstart = wstart;
+            p.touched = 0;
+            out[at] = p;
+        });
     }
 }

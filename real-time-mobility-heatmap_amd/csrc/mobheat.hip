@@ -3,6 +3,7 @@
 // One translation unit (the device code shares __constant__ tables and inlines across stages); its parts, in
 // dependency order:
 //   dev_common.h    wave primitives, per-window state-table lookups, census sinks, the batch's window registry
+//   dev_table.h     the off-hot-path global hash tables' probe loop (tab_probe), the live-slot compaction (block256_compact)
 //   k_partition.h   radix partition into (window, region) bins / owner ranks (k_ev_hist, k_ev_scatter_rec, k_rp_*)
 //   k_table.h       table mode for low-cardinality batches (k_agg, k_bin_reduce)
 //   k_merge.h       census, growth dump, the region-owned merge into the update-mode state (k_merge_owned), rows
@@ -74,6 +75,7 @@ static hipError_t upload_tables() {
 }
 
 #include "dev_common.h"
+#include "dev_table.h"
 #include "k_partition.h"
 #include "k_table.h"
 #include "k_merge.h"

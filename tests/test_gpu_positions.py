@@ -159,6 +159,32 @@ def test_growth_over_four_batches():
         eng.close()
 
 
+@pytest.mark.parametrize("keys", [1, 512, 513, 1025])
+def test_export_at_the_compaction_edges(keys):
+    """one row for each of `keys` distinct pairs: the pair table has next_pow2(max(2 * keys, 1024)) = 1024, 1024, 2048,
+    4096 slots -- less than one 2048-slot tile of the export's compaction (the i < nslots guard), the same at load
+    exactly 1/2, exactly one tile, two workgroups on one counter.  Then new pairs (600, or what it takes to pass load 1/2)
+    take the state to the next table size: the old tables' slots are claimed again in the new ones (k_pos_pair_put,
+    k_pos_str_rehash)."""
+    eng = _engine()
+    try:
+        cap0 = max(1024, 1 << (2 * keys - 1).bit_length())
+        more = max(600, cap0 // 2 - keys + 100)
+        rng = np.random.default_rng(keys)
+        lat, lon = _coords(rng, keys + more)
+        rows = [(f"p{k % 3}", f"v{k}", T0 + k * SEC, lat[k], lon[k]) for k in range(keys + more)]
+        state = _check_sequence(eng, [Batch(rows[:keys])])
+        info = eng.positions_info()
+        assert info["keys"] == len(state) == keys
+        assert info["capacity"] == cap0
+        _check_sequence(eng, [Batch(rows[keys:])], state, 1)
+        info = eng.positions_info()
+        assert info["keys"] == len(state) == keys + more
+        assert info["capacity"] > cap0 and info["pair_regrows"] >= 1
+    finally:
+        eng.close()
+
+
 @pytest.mark.parametrize("case", [case_one_batch, case_codes_move, case_strings])
 def test_colliding_hashes_stay_exact(case):
     """string hashes cut to 4 bits: unequal strings with equal hashes everywhere; equal hash + unequal bytes probes on"""

@@ -138,6 +138,31 @@ def test_lds_spill_regime_dyadic():
         eng.close()
 
 
+def test_output_cap_met_exactly_dyadic():
+    """A window of a few thousand distinct res-8 cells rolled up at res == h3_res: every key is its own parent, so the
+    output cap equals the record count and the last record lands on the last place (at < out_cap with nothing to
+    spare); then at res 0, where a handful of records leave the same compaction."""
+    from mobheat import HeatmapEngine
+    rng = np.random.default_rng(3108)
+    n = 5000
+    lat = rng.integers(-90 * 1024, 90 * 1024 + 1, n) / 1024.0
+    lon = rng.integers(-180 * 1024, 180 * 1024 + 1, n) / 1024.0
+    eng = HeatmapEngine(h3_res=8)
+    try:
+        eng.process_batch(0, **_batch(rng, lat, lon, T0 + rng.integers(0, 5 * MINUTE, n), dyadic=True))
+        _, recs = eng.export_state()
+        wins, keys = eng.live_windows()
+        assert wins.tolist() == [T0] and keys.tolist() == [recs.size] and 3000 < recs.size <= n
+        for r in (8, 0):
+            got = eng.window_records(T0, r)
+            exp = expected(recs, T0, r)
+            assert got.size == exp.size
+            check_rollup(got, exp, exact_sums=True, what=f"res 8 -> {r}")
+        assert eng.window_records(T0, 8).size == recs.size and eng.window_records(T0, 0).size <= 122
+    finally:
+        eng.close()
+
+
 def test_hot_parents_dyadic(oracle_h3):
     """300k rows on a 1/4096-degree lattice inside ONE res-2 cell (a box around the cell's centre, well inside its
     inradius), engine at res 10 (~2.6e5 keys, a table scanned by > 100 workgroups): rolled up to 2, 1 and 0 every
