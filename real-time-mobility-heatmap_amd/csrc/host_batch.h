@@ -21,7 +21,9 @@ static bool choose_binned(const hm_ctx *ctx, int64_t n) {
 // 10% room, covers a stream whose clustering is steady)
 static unsigned slab_cap_for(int64_t n, double skew, int64_t nbins) {
     const int64_t m = (n + nbins - 1) / nbins;
-    const int64_t c = std::max<int64_t>(m + m / 4 + 256, (int64_t)(skew * 1.1 * (double)m) + 256);
+    // (no bin holds more than the batch's n rows: after a batch of one row -- skew = nbins -- the next small batch
+    // pinned to the binned path asked for nbins x 1.1 nbins records, 38 GB in sub-bins)
+    const int64_t c = std::min<int64_t>(std::max<int64_t>(m + m / 4 + 256, (int64_t)(skew * 1.1 * (double)m) + 256), n + 256);
     return (unsigned)std::min<int64_t>((c + 1) & ~int64_t(1), (int64_t)UINT32_MAX / 2);   // (even: 64-B aligned slabs)
 }
 
@@ -329,10 +331,15 @@ static int merge_nothing(hm_ctx *ctx) {
 static int merge_partials(hm_ctx *ctx, const TilePartial *parts, int64_t n_parts) {
     int rc;
     ctx->n_partials_merged = n_parts;
+    std::vector<WinCount> census;
+    // table mode counted its census already (phase_table): too many live windows are refused before the merge begins,
+    // the state and its version as they were (the stage merge counts below, after merge_begin's reset of the counters)
+    const bool counted = n_parts > 0 && ctx->census_ready;
+    if (counted && ((rc = census_of_partials(ctx, parts, n_parts, census)) || (rc = windows_fit(ctx, census)))) return rc;
     if ((rc = merge_begin(ctx, n_parts))) return rc;
     if (n_parts == 0) { ctx->census_ready = false; return merge_nothing(ctx); }
-    std::vector<WinCount> census;
-    if ((rc = census_of_partials(ctx, parts, n_parts, census)) || (rc = gens_prepare(ctx, census))) return rc;
+    if (!counted && (rc = census_of_partials(ctx, parts, n_parts, census))) return rc;
+    if ((rc = gens_prepare(ctx, census))) return rc;
     HIPCHK(ctx, hipEventRecord(ctx->ev[3], ctx->stream));
     int64_t ntiles;
     if ((rc = partition<TilePartial, SortedRec>(ctx, parts, n_parts, ntiles))) return rc;
@@ -368,11 +375,15 @@ static int bin_offsets(hm_ctx *ctx) {
 static int merge_events(hm_ctx *ctx, const Inputs &I, int64_t n_rec) {
     int rc;
     ctx->n_partials_merged = n_rec;
+    // (too many live windows: refused before the merge begins, the state and its version as they were)
+    std::vector<WinCount> census;
+    if (n_rec > 0) {
+        census_of_registry(ctx, census);
+        if ((rc = windows_fit(ctx, census))) return rc;
+    }
     if ((rc = merge_begin(ctx, I.n, true))) return rc;   // (only k_ingest, k_sample_heavy and the side stream's
                                                           // k_dedup_flag ran since k_batch_reset: none counts these)
     if (n_rec == 0) return merge_nothing(ctx);
-    std::vector<WinCount> census;
-    census_of_registry(ctx, census);
     // binned in k_ingest: every window's table in range geometry (a row's bin is its region), and the bins' row
     // offsets are the exclusive scan of their cursors -- no partition pass over the keys and columns
     const bool binned = ctx->binned;

@@ -832,6 +832,19 @@ static int winfo_upload(hm_ctx *ctx, bool with_bins) {
     return HM_OK;
 }
 
+// The census's new windows and the live ones fit the window map (GMAP_SLOTS / 2): checked before a table is acquired or
+// a window joins ctx->gens -- a batch refused here leaves the state as it was (the windows it would have added were
+// once kept, with no keys, and every later batch was refused with them), and, where the caller asks before
+// merge_begin, hm_state_version too
+static int windows_fit(hm_ctx *ctx, const std::vector<WinCount> &census) {
+    size_t fresh = 0;
+    for (const WinCount &w : census)
+        fresh += std::none_of(ctx->gens.begin(), ctx->gens.end(), [&](const hm_ctx::Gen &g) { return g.wenc == w.wenc; });
+    if (ctx->gens.size() + fresh > (size_t)(GMAP_SLOTS / 2))
+        return set_err(ctx, HM_E_OVERFLOW, "%zu live windows exceed the window map (%d)", ctx->gens.size() + fresh, GMAP_SLOTS / 2);
+    return HM_OK;
+}
+
 // Give every window of the census a table large enough for its keys after this batch (new windows: a new table;
 // windows that would pass load 1/2: a larger table, filled by dumping the old one and merging the dump in rehash
 // mode); upload the window map.
@@ -843,6 +856,7 @@ static int gens_prepare(hm_ctx *ctx, const std::vector<WinCount> &census, bool r
     range = range_mode(ctx, range);
     unsigned lo = 0, hi = 0;
     range_of(ctx, lo, hi);
+    if ((rc = windows_fit(ctx, census))) return rc;
     for (auto &g : ctx->gens) g.batch_parts = 0;
     for (const WinCount &w : census) {
         ctx->batch_windows.push_back(wdec(w.wenc));
@@ -867,8 +881,6 @@ static int gens_prepare(hm_ctx *ctx, const std::vector<WinCount> &census, bool r
         }
         it->batch_parts = c;
     }
-    if ((int)ctx->gens.size() > GMAP_SLOTS / 2)
-        return set_err(ctx, HM_E_OVERFLOW, "%zu live windows exceed the window map (%d)", ctx->gens.size(), GMAP_SLOTS / 2);
     if ((rc = gens_upload(ctx))) return rc;
     if (!old.empty()) {
         int64_t moved = 0;
