@@ -30,6 +30,8 @@
  *                                   engine's state instead of MongoDB, at any H3 resolution <= H3_RES.
  *   hm_positions_*               -- the positions_latest collection itself (:217-228 and app.py:71-88): every vehicle's
  *                                   newest position so far, folded across batches on the device.
+ *   hm_window_geojson / hm_positions_geojson -- the two endpoints' response bodies (app.py:45-88) as GeoJSON encoded on
+ *                                   the GPU, byte for byte json.dumps of the collections the reference builds in Python.
  */
 #ifndef MOBHEAT_H
 #define MOBHEAT_H
@@ -506,6 +508,81 @@ int hm_positions_info(const hm_ctx *ctx, int64_t *v, int32_t n);
 /* Test seam: every string hash is cut to its low `bits` bits (0..64; 64 = off), so that unequal strings with equal
  * hashes are the common case.  Results stay exact.  Only while the state is empty (HM_E_STATE otherwise). */
 int hm_positions_debug_hash_bits(hm_ctx *ctx, int32_t bits);
+
+/* ---- the read side's response bodies as GeoJSON, encoded on the GPU (reference app.py:45-88: api_tiles_latest /
+ * api_positions_latest build one dict per tile / vehicle and json.dumps walks them) ----
+ * Every call returns one contiguous response body and the features' offsets in it:
+ *   bytes[0, 40)                      {"type":"FeatureCollection","features":[
+ *   bytes[offsets[i], offsets[i+1]-1) feature i, exactly json.dumps(feature, separators=(",", ":")) of the feature
+ *                                     mobheat/readside.py builds (ensure_ascii, NaN / Infinity / -Infinity as json.dumps)
+ *   bytes[offsets[i+1]-1]             ',' after every feature but the last, ']' after the last
+ *   bytes[offsets[n]]                 '}'
+ * offsets has n + 1 entries, offsets[0] = 40.  The body is bytes[0, offsets[n] + 1) for n >= 1.  For n == 0 there is no
+ * separator slot: offsets[0] = 40 and the body is the 42 bytes {"type":"FeatureCollection","features":[]}, so the body
+ * length is offsets[n] + (n ? 1 : 2) and a caller never reads past "]}".  Doubles are written as Python's float.__repr__
+ * writes them (shortest round-trip digits, csrc/float_repr.h).  Outputs are library-owned, in device or pinned host
+ * memory per out_memory (HM_MEM_DEVICE / HM_MEM_HOST), valid until the next call on the context; the encoders use
+ * buffers of their own (a streamed statement encode and a checkpoint export in progress are unaffected), and a repeated
+ * call of the same size allocates nothing.  Not between stage calls (HM_E_STATE).
+ *
+ * Tile feature (one call = one window, so the two window texts are per call):
+ *   {"type":"Feature","geometry":{"type":"Polygon","coordinates":[[[lng,lat],...]]},"properties":{"cellId":"<hex>",
+ *    "count":<int>,"avgSpeedKmh":<repr>,"windowStart":"<text>","windowEnd":"<text>"}}
+ * ring: the cell's boundary (hm_cells_to_boundary: upstream order, degrees), the first vertex repeated at the end iff
+ * there is one and it differs from the last by value; an invalid cell index gives "coordinates":[[]].  cellId =
+ * format(cell, "x"); count in decimal; avgSpeedKmh = 0.0 when n_speed == 0, else sum_speed / n_speed (IEEE binary64
+ * division; a NaN sum prints NaN).  window_start_text / window_end_text: the caller's pre-formatted ASCII, e.g.
+ * datetime.isoformat() of the wall time, at most 40 bytes each of 0x20-0x7e without '"' and '\' (HM_E_INVALID otherwise). */
+typedef struct hm_geojson_cfg {
+    const char *window_start_text;
+    int32_t start_len;
+    const char *window_end_text;
+    int32_t end_len;
+} hm_geojson_cfg;
+/* the features of n caller records (recs in host or device memory per `memory`; window_start_us, sums of lat / lon and
+ * reserved are not read) */
+int hm_encode_tile_features(hm_ctx *ctx, const hm_geojson_cfg *cfg, int64_t n, int32_t memory, const hm_state_rec *recs,
+                            int32_t out_memory, const uint8_t **bytes, const int64_t **offsets);
+/* hm_window_rollup of live window window_start_us at res (same validity rules, same errors; a window that is not live:
+ * *n = 0 and the empty body) and its records' features, the records never leaving the device.  recs (optional): the
+ * records in feature order, pinned host memory.  Reads the tile state only: hm_state_version, the next batch and a
+ * checkpoint export in progress are unaffected. */
+int hm_window_geojson(hm_ctx *ctx, int64_t window_start_us, int32_t res, const hm_geojson_cfg *cfg, int32_t out_memory,
+                      const uint8_t **bytes, const int64_t **offsets, int64_t *n, const hm_state_rec **recs);
+/* Host execution of the same encoder (no GPU): the whole body into bytes (cap bytes: HM_E_INVALID if they do not
+ * suffice, at least 42), offsets n + 1 entries. */
+int hm_selftest_tile_features(const hm_geojson_cfg *cfg, const hm_state_rec *recs, int64_t n, uint8_t *bytes, int64_t cap,
+                              int64_t *offsets);
+
+/* Position feature, from the positions state S (hm_positions_update):
+ *   {"type":"Feature","geometry":{"type":"Point","coordinates":[lon,lat]},"properties":{"provider":"..","vehicleId":"..",
+ *    "ts":"YYYY-MM-DDTHH:MM:SS[.ffffff]"}}
+ * The strings come from S's persistent dictionaries, escaped as json.dumps(ensure_ascii=True) escapes them (\" \\ \n \r
+ * \t \b \f, every other byte below 0x20, 0x7f and every non-ASCII code point as \uxxxx in lowercase hex, a code point
+ * above U+FFFF as a surrogate pair); a string that is not valid UTF-8 fails the call (HM_E_INVALID).  ts =
+ * datetime.isoformat() of the naive wall time of ts_us shifted by the local offset of its 900-s bucket floor(ts_s / 900)
+ * (bucket_ids / bucket_offset_s of hm_position_doc_cfg, strictly ascending; the other fields are not read); the fraction
+ * only when the microseconds are non-zero.  A record whose bucket is absent, or a local year outside 1..9999: HM_E_INVALID.
+ * Neither call touches the tile state or S.  A shard context (shard_count > 1): HM_E_UNSUPPORTED, as hm_positions_update. */
+/* the distinct 900-s buckets of S's ts, ascending (*n = count; up to cap written) */
+int hm_positions_buckets(hm_ctx *ctx, int64_t *bucket_ids, int64_t cap, int64_t *n);
+/* recs (optional): S's records in feature order, pinned host memory (codes index hm_positions_export's dictionaries) */
+int hm_positions_geojson(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t out_memory, const uint8_t **bytes,
+                         const int64_t **offsets, int64_t *n, const hm_position_rec **recs);
+/* Host execution of the same encoder on caller records, dictionaries (Arrow offsets + bytes) and buckets (no GPU); a
+ * record outside the dictionaries or buckets, a bad string or year, or cap too small: HM_E_INVALID. */
+int hm_selftest_position_features(const hm_position_doc_cfg *cfg, const hm_position_rec *recs, int64_t n, uint8_t *bytes,
+                                  int64_t cap, int64_t *offsets);
+/* up to n of, for the last GeoJSON call on the context (HIP events): [0] its sizes kernel (for tiles: the boundaries
+ * included), microseconds, [1] its write kernel, [2] from the first kernel to the last, the offsets' scan and its
+ * read-back included, [3] the body's length in bytes. */
+int hm_geojson_info(const hm_ctx *ctx, int64_t *v, int32_t n);
+
+/* json.dumps(x) of n doubles -- CPython's float.__repr__, NaN / Infinity / -Infinity for the non-finite -- as the GeoJSON
+ * encoders write them (csrc/float_repr.h), executed on the host and on GPU `device` (test entry points): value i's
+ * len[i] <= 24 bytes at text[24 i]. */
+int hm_selftest_float_repr_host(const double *x, int64_t n, uint8_t *text, int32_t *len);
+int hm_selftest_float_repr_device(const double *x, int64_t n, uint8_t *text, int32_t *len, int32_t device);
 
 /* Counts of the last hm_process_batch / stage batch (up to n of them): [0] keys created in the tile state, [1] partial
  * records merged (direct path: aggregated rows; table mode: ~ distinct keys; stage API: the records this rank

@@ -215,6 +215,7 @@ void hm_destroy(hm_ctx *ctx) {
         if (d->h_bytes) (void)hipHostFree(d->h_bytes);
     }
     positions_free(ctx);
+    geojson_free(ctx);
     for (auto &g : ctx->gens)
         if (!in_arena(ctx, g.tab)) (void)hipFree(g.tab);
     for (auto &pt : ctx->pool)

@@ -20,16 +20,14 @@ int hm_live_windows(hm_ctx *ctx, int64_t *window_start_us, int64_t *keys, int64_
 
 // One pass over the window's table (k_rollup) into a zeroed parent table, then the compaction (k_rollup_emit); buffers
 // of its own (ru_tab, ru_out, h_ru), so that a checkpoint dump waiting in parts_regrow stays as it is.
-int hm_window_rollup(hm_ctx *ctx, int64_t window_start_us, int32_t res, int32_t out_memory, const hm_state_rec **recs,
-                     int64_t *n) {
+// Leaves *m_out records of window window_start_us at res in ctx->ru_out (0: the window is not live); `who` names the
+// entry point in the errors (hm_window_rollup, and hm_window_geojson, which encodes the records where they are).
+static int rollup_on_device(hm_ctx *ctx, int64_t window_start_us, int32_t res, const char *who, int64_t *m_out) {
     static_assert(sizeof(hm_state_rec) == sizeof(GrowRec), "hm_state_rec mirrors GrowRec");
-    if (!ctx || !recs || !n || (out_memory != HM_MEM_HOST && out_memory != HM_MEM_DEVICE))
-        return ctx ? set_err(ctx, HM_E_INVALID, "bad argument") : HM_E_INVALID;
     if (res < 0 || res > ctx->cfg.h3_res)
         return set_err(ctx, HM_E_INVALID, "roll-up resolution %d outside 0..%d", res, ctx->cfg.h3_res);
-    if (ctx->stage != 0) return set_err(ctx, HM_E_STATE, "hm_window_rollup between stage calls");
-    *recs = nullptr;
-    *n = 0;
+    if (ctx->stage != 0) return set_err(ctx, HM_E_STATE, "%s between stage calls", who);
+    *m_out = 0;
     const hm_ctx::Gen *gen = nullptr;
     for (const auto &g : ctx->gens)
         if (g.wenc == wenc_of(window_start_us) && g.keys > 0) gen = &g;
@@ -59,7 +57,20 @@ int hm_window_rollup(hm_ctx *ctx, int64_t window_start_us, int32_t res, int32_t 
     if (got[1]) return set_err(ctx, HM_E_OVERFLOW, "roll-up parent table of %lld slots overflowed", (long long)nslots);
     if ((int64_t)got[0] > bound)
         return set_err(ctx, HM_E_STATE, "roll-up found %llu parents, at most %lld expected", got[0], (long long)bound);
-    const int64_t m = (int64_t)got[0];
+    *m_out = (int64_t)got[0];
+    return HM_OK;
+}
+
+int hm_window_rollup(hm_ctx *ctx, int64_t window_start_us, int32_t res, int32_t out_memory, const hm_state_rec **recs,
+                     int64_t *n) {
+    if (!ctx || !recs || !n || (out_memory != HM_MEM_HOST && out_memory != HM_MEM_DEVICE))
+        return ctx ? set_err(ctx, HM_E_INVALID, "bad argument") : HM_E_INVALID;
+    *recs = nullptr;
+    *n = 0;
+    int64_t m = 0;
+    int rc;
+    if ((rc = rollup_on_device(ctx, window_start_us, res, "hm_window_rollup", &m))) return rc;
+    if (m == 0) return HM_OK;
     if (out_memory == HM_MEM_HOST) {
         if ((rc = host_pinned(ctx, &ctx->h_ru, ctx->h_ru_cap, (size_t)std::max<int64_t>(m, 1) * sizeof(GrowRec)))) return rc;
         if (m > 0) {

@@ -229,3 +229,45 @@ int hm_selftest_glibc_libm_device(int32_t fn, const double *a, const double *b, 
         if (p) (void)hipFree(p);
     return rc;
 }
+
+// json.dumps of doubles (float_repr.h), executed on the host and on the GPU (tests/test_float_repr_host.py,
+// tests/test_gpu_geojson.py): value i's text at text[24 i], its length in len[i]
+__global__ __launch_bounds__(256) void k_float_repr(const double *__restrict__ x, int64_t n, uint8_t *__restrict__ text,
+                                                    int32_t *__restrict__ len) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        len[i] = float_repr(x[i], text + FLOAT_REPR_MAX * i);
+}
+
+int hm_selftest_float_repr_host(const double *x, int64_t n, uint8_t *text, int32_t *len) {
+    if (n < 0 || (n > 0 && (!x || !text || !len))) return HM_E_INVALID;
+    for (int64_t i = 0; i < n; i++) len[i] = float_repr(x[i], text + FLOAT_REPR_MAX * i);
+    return HM_OK;
+}
+
+int hm_selftest_float_repr_device(const double *x, int64_t n, uint8_t *text, int32_t *len, int32_t device) {
+    if (n < 0 || (n > 0 && (!x || !text || !len))) return HM_E_INVALID;
+    int ndev = 0;
+    if (device < 0 || hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev || hipSetDevice(device) != hipSuccess)
+        return HM_E_HIP;
+    if (n == 0) return HM_OK;
+    double *dx = nullptr;
+    uint8_t *dt = nullptr;
+    int32_t *dl = nullptr;
+    int rc = HM_OK;
+    if (hipMalloc((void **)&dx, (size_t)n * 8) != hipSuccess || hipMalloc((void **)&dt, (size_t)n * FLOAT_REPR_MAX) != hipSuccess ||
+        hipMalloc((void **)&dl, (size_t)n * 4) != hipSuccess)
+        rc = HM_E_NOMEM;
+    if (rc == HM_OK && (hipMemcpy(dx, x, (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess ||
+                        hipMemset(dt, 0, (size_t)n * FLOAT_REPR_MAX) != hipSuccess))
+        rc = HM_E_HIP;
+    if (rc == HM_OK) {
+        hipLaunchKernelGGL(k_float_repr, dim3(grid_for(n, 256)), dim3(256), 0, 0, dx, n, dt, dl);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(text, dt, (size_t)n * FLOAT_REPR_MAX, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(len, dl, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = HM_E_HIP;
+    }
+    for (void *p : {(void *)dx, (void *)dt, (void *)dl})
+        if (p) (void)hipFree(p);
+    return rc;
+}

@@ -167,6 +167,18 @@ struct hm_ctx {
         hipEvent_t ev[3] = {};
         double us[2] = {0, 0};
     } pos;
+    // hm_encode_tile_features / hm_window_geojson / hm_positions_* as GeoJSON (api_geojson.h, k_geojson.h): buffers of
+    // their own, so that a streamed statement encode (td_*) and a waiting checkpoint dump stay as they are.  Nothing
+    // here is allocated before the first such call.
+    struct GeoJson {
+        DevBuf in, verts, vn, sizes, off, btot, boff, bytes, words, precs, params, bset, blist;
+        void *h_bytes = nullptr, *h_off = nullptr, *h_recs = nullptr;   // pinned host copies
+        size_t h_bytes_cap = 0, h_off_cap = 0, h_recs_cap = 0;
+        hipEvent_t ev[4] = {};   // before / after the sizes kernel, before / after the write kernel
+        bool ready = false;
+        double us[3] = {0, 0, 0};   // the last call's sizes kernel, write kernel, first to last event
+        int64_t last_bytes = 0;     // the last call's body length
+    } gj;
     DevBuf keys;                     // k_ingest's event key per row (kernels.h ekey)
     // k_ingest's fused binning (large direct-path batches): the bins' cursors (RP_BINS + 1 u32: the last stays 0, so
     // that their exclusive scan ends with the total) and the slab capacity; the slabs are parts_sorted
@@ -283,6 +295,18 @@ static void positions_free(hm_ctx *ctx) {
     for (void *p : {P.h_recs, P.h_off[0], P.h_off[1], P.h_bytes[0], P.h_bytes[1]})
         if (p) (void)hipHostFree(p);
     for (auto &e : P.ev)
+        if (e) (void)hipEventDestroy(e);
+}
+
+// hm_destroy's part for the GeoJSON encoders
+static void geojson_free(hm_ctx *ctx) {
+    hm_ctx::GeoJson &G = ctx->gj;
+    for (DevBuf *b : {&G.in, &G.verts, &G.vn, &G.sizes, &G.off, &G.btot, &G.boff, &G.bytes, &G.words, &G.precs, &G.params,
+                      &G.bset, &G.blist})
+        if (b->p) (void)hipFree(b->p);
+    for (void *p : {G.h_bytes, G.h_off, G.h_recs})
+        if (p) (void)hipHostFree(p);
+    for (auto &e : G.ev)
         if (e) (void)hipEventDestroy(e);
 }
 

@@ -208,24 +208,28 @@ __global__ __launch_bounds__(256) void k_json_patch(const JsonPatchRow *__restri
         vkey[i] = p.rv ? (uint64_t)p.pcode * nv + (uint64_t)p.vcode : 0;
     }
 }
-// the distinct 900-s buckets of the latest rows' eventTs (a set of int64, EMPTY = INT64_MIN), compacted into list
+// the 900-s bucket of an eventTs added to a set of int64 (EMPTY = INT64_MIN); the first to add it appends it to list
+__device__ __forceinline__ void bucket_set_add(int64_t ts_us, long long *set, unsigned long long mask, long long *list,
+                                               unsigned long long *n_list) {
+    const long long b = (long long)floordiv(floordiv(ts_us, 1000000), 900);
+    unsigned long long s = mix64((uint64_t)b) & mask;
+    for (unsigned long long p = 0; p <= mask; p++) {
+        long long k = __hip_atomic_load(&set[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (k == INT64_MIN) {
+            k = atomicCAS((unsigned long long *)&set[s], (unsigned long long)INT64_MIN, (unsigned long long)b);
+            if (k == INT64_MIN) { list[atomicAdd(n_list, 1ull)] = b; break; }
+        }
+        if (k == b) break;
+        s = (s + 1) & mask;
+    }
+}
+// the distinct 900-s buckets of the latest rows' eventTs, compacted into list
 __global__ __launch_bounds__(256) void k_latest_buckets(const int64_t *__restrict__ rows, int64_t m,
                                                         const int64_t *__restrict__ ts, long long *set, unsigned long long mask,
                                                         long long *list, unsigned long long *n_list) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < m; q += stride) {
-        const long long b = (long long)floordiv(floordiv(ts[rows[q]], 1000000), 900);
-        unsigned long long s = mix64((uint64_t)b) & mask;
-        for (unsigned long long p = 0; p <= mask; p++) {
-            long long k = __hip_atomic_load(&set[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (k == INT64_MIN) {
-                k = atomicCAS((unsigned long long *)&set[s], (unsigned long long)INT64_MIN, (unsigned long long)b);
-                if (k == INT64_MIN) { list[atomicAdd(n_list, 1ull)] = b; break; }
-            }
-            if (k == b) break;
-            s = (s + 1) & mask;
-        }
-    }
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < m; q += stride)
+        bucket_set_add(ts[rows[q]], set, mask, list, n_list);
 }
 __global__ __launch_bounds__(256) void k_fill_i64(long long *p, int64_t n, long long v) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;

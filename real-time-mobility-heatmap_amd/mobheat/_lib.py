@@ -95,6 +95,11 @@ class HmPositionDocCfg(ctypes.Structure):
                 ("n_buckets", c_i64), ("bucket_ids", c_vp), ("bucket_offset_s", c_vp)]
 
 
+class HmGeojsonCfg(ctypes.Structure):
+    _fields_ = [("window_start_text", ctypes.c_char_p), ("start_len", c_i32), ("window_end_text", ctypes.c_char_p),
+                ("end_len", c_i32)]
+
+
 # hm_state_rec (64 B): one live (cellId, windowStart) key of the tile state
 STATE_REC_DTYPE = np.dtype([("cell", "<u8"), ("window_start_us", "<i8"), ("count", "<i8"), ("n_speed", "<i8"),
                             ("sum_speed", "<f8"), ("sum_lat", "<f8"), ("sum_lon", "<f8"), ("reserved", "<i8")])
@@ -166,6 +171,15 @@ SIGNATURES = {
     "hm_positions_import": (c_i32, [c_vp, c_vp, c_i64, _P(HmPositionDocCfg)]),
     "hm_positions_info": (c_i32, [c_vp, c_vp, c_i32]),
     "hm_positions_debug_hash_bits": (c_i32, [c_vp, c_i32]),
+    "hm_encode_tile_features": (c_i32, [c_vp, _P(HmGeojsonCfg), c_i64, c_i32, c_vp, c_i32, _P(c_vp), _P(c_vp)]),
+    "hm_window_geojson": (c_i32, [c_vp, c_i64, c_i32, _P(HmGeojsonCfg), c_i32, _P(c_vp), _P(c_vp), _P(c_i64), _P(c_vp)]),
+    "hm_selftest_tile_features": (c_i32, [_P(HmGeojsonCfg), c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "hm_positions_buckets": (c_i32, [c_vp, c_vp, c_i64, _P(c_i64)]),
+    "hm_positions_geojson": (c_i32, [c_vp, _P(HmPositionDocCfg), c_i32, _P(c_vp), _P(c_vp), _P(c_i64), _P(c_vp)]),
+    "hm_selftest_position_features": (c_i32, [_P(HmPositionDocCfg), c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "hm_geojson_info": (c_i32, [c_vp, c_vp, c_i32]),
+    "hm_selftest_float_repr_host": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
+    "hm_selftest_float_repr_device": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32]),
     "hm_abi_version": (c_i32, []),
 }
 
@@ -461,3 +475,86 @@ def cells_to_boundary_host_selftest(cells):
     check(lib.hm_selftest_cells_to_boundary_host(ptr(cells), cells.size, ptr(la), ptr(lo), ptr(nv)), None,
           "hm_selftest_cells_to_boundary_host")
     return la, lo, nv
+
+
+# ---- the read side's GeoJSON bodies (csrc/geojson_docs.h, csrc/float_repr.h) ----
+GEOJSON_PREFIX = b'{"type":"FeatureCollection","features":['
+
+
+def geojson_body_len(offsets):
+    """Length of the response body whose features' offsets are `offsets` (n + 1 entries): offsets[n] + 1, or the 42
+    bytes of the empty collection when n == 0 (include/mobheat.h)."""
+    n = len(offsets) - 1
+    return int(offsets[n]) + (1 if n else 2)
+
+
+def float_repr_selftest(x, device=None):
+    """json.dumps of each double as csrc/float_repr.h writes it, executed on the host (device=None) or on GPU `device`:
+    a list of bytes."""
+    lib = load()
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    text = np.zeros((x.size, 24), np.uint8)
+    ln = np.zeros(x.size, np.int32)
+    if device is None:
+        check(lib.hm_selftest_float_repr_host(ptr(x), x.size, ptr(text), ptr(ln)), None, "hm_selftest_float_repr_host")
+    else:
+        check(lib.hm_selftest_float_repr_device(ptr(x), x.size, ptr(text), ptr(ln), int(device)), None,
+              "hm_selftest_float_repr_device")
+    return text, ln
+
+
+def geojson_cfg(window_start_text, window_end_text):
+    """hm_geojson_cfg for the two window texts (str or bytes); the returned tuple keeps the bytes alive."""
+    a = window_start_text.encode("utf-8") if isinstance(window_start_text, str) else bytes(window_start_text)
+    b = window_end_text.encode("utf-8") if isinstance(window_end_text, str) else bytes(window_end_text)
+    return HmGeojsonCfg(window_start_text=a, start_len=len(a), window_end_text=b, end_len=len(b)), (a, b)
+
+
+def tile_features_selftest(recs, window_start_text, window_end_text):
+    """Host execution of the GPU tile-feature encoder on STATE_REC_DTYPE records (no GPU): (body uint8, offsets int64)."""
+    lib = load()
+    recs = np.ascontiguousarray(recs, dtype=STATE_REC_DTYPE)
+    cfg, keep = geojson_cfg(window_start_text, window_end_text)
+    cap = 64 + 880 * recs.size
+    buf = np.zeros(cap, np.uint8)
+    offs = np.zeros(recs.size + 1, np.int64)
+    check(lib.hm_selftest_tile_features(ctypes.byref(cfg), ptr(recs) if recs.size else None, recs.size, ptr(buf), cap,
+                                        ptr(offs)), None, "hm_selftest_tile_features")
+    return buf[:geojson_body_len(offs)].copy(), offs
+
+
+def bucket_cfg(bucket_ids, tz=None):
+    """hm_position_doc_cfg holding only the 900-s buckets and their local offsets: the process's zone (time_buckets), or
+    zone tz's; the returned tuple keeps the arrays alive."""
+    if tz is None:
+        bi, bo = time_buckets(None, np.asarray(bucket_ids, np.int64))
+    else:
+        import datetime as _dt
+        bi = np.unique(np.asarray(bucket_ids, dtype=np.int64))
+
+        def off(s):
+            return int(_dt.datetime.fromtimestamp(s, tz).utcoffset().total_seconds())
+        bo = np.array([off(int(b) * 900) for b in bi], np.int64)
+        if any(off(int(b) * 900 + 899) != o for b, o in zip(bi, bo)):
+            raise RuntimeError("a local-time offset change inside a 900-s bucket")
+    bi, bo = np.ascontiguousarray(bi, np.int64), np.ascontiguousarray(bo, np.int64)
+    cfg = HmPositionDocCfg(n_buckets=bi.size, bucket_ids=ptr(bi) if bi.size else None,
+                           bucket_offset_s=ptr(bo) if bo.size else None)
+    return cfg, (bi, bo)
+
+
+def position_features_selftest(recs, providers, vehicles, bucket_ids, bucket_offset_s):
+    """Host execution of the GPU position-feature encoder (no GPU) on POSITION_REC_DTYPE records, the two dictionaries
+    ((n, offsets, bytes), so that any byte string can be given) and the bucket table: (body uint8, offsets int64)."""
+    lib = load()
+    recs = np.ascontiguousarray(recs, dtype=POSITION_REC_DTYPE)
+    cfg, keep = position_dicts_cfg(providers, vehicles)
+    bi = np.ascontiguousarray(bucket_ids, np.int64)
+    bo = np.ascontiguousarray(bucket_offset_s, np.int64)
+    cfg.n_buckets, cfg.bucket_ids, cfg.bucket_offset_s = bi.size, ptr(bi) if bi.size else None, ptr(bo) if bo.size else None
+    cap = 64 + recs.size * 256 + 12 * recs.size * int(max(keep[1].size, 1) + max(keep[3].size, 1))
+    buf = np.zeros(cap, np.uint8)
+    offs = np.zeros(recs.size + 1, np.int64)
+    check(lib.hm_selftest_position_features(ctypes.byref(cfg), ptr(recs) if recs.size else None, recs.size, ptr(buf), cap,
+                                            ptr(offs)), None, "hm_selftest_position_features")
+    return buf[:geojson_body_len(offs)].copy(), offs

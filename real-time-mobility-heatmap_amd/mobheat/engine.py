@@ -297,6 +297,100 @@ class HeatmapEngine:
         return TileRows(cell=r["cell"].astype(np.uint64), window_start_us=ws, window_end_us=ws + self.tile_us, count=cnt,
                         avg_speed=avg_speed, speed_null=~has, avg_lon=r["sum_lon"] / cnt, avg_lat=r["sum_lat"] / cnt)
 
+    # ---- the read side's response bodies, GeoJSON-encoded on the GPU (hm_window_geojson / hm_positions_geojson) ----
+    @staticmethod
+    def _geojson_body(pb, po, n, copy):
+        offs = np.ctypeslib.as_array(ctypes.cast(po, ctypes.POINTER(ctypes.c_int64)), shape=(n + 1,))
+        raw = np.ctypeslib.as_array(ctypes.cast(pb, ctypes.POINTER(ctypes.c_uint8)), shape=(_lib.geojson_body_len(offs),))
+        return raw.tobytes() if copy else memoryview(raw)
+
+    def window_geojson(self, window_start_us=None, res=None, tz=None, copy=True, with_records=False):
+        """The body of /api/tiles/latest for one live window (None: the newest) at H3 resolution res <= h3_res (None:
+        h3_res): json.dumps(readside.tiles_latest_collection(...), separators=(",", ":")) as bytes, rolled up and
+        encoded on the GPU in one call.  windowStart / windowEnd are formatted as readside.tile_docs_from_engine formats
+        them (stream._spark_datetime, or zone tz's wall time).  copy=False: a memoryview of the library's pinned buffer,
+        valid until the next call on this engine.  with_records: (body, records in feature order, offsets) instead."""
+        import datetime as _dt
+
+        from .stream import _spark_datetime
+
+        def when(us):
+            us = int(us)
+            if tz is None:
+                return _spark_datetime(us).isoformat()
+            return _dt.datetime.fromtimestamp(us // 1000000, tz).replace(tzinfo=None, microsecond=us % 1000000).isoformat()
+        res = self.h3_res if res is None else int(res)
+        if window_start_us is None:
+            ws, _ = self.live_windows()
+            window_start_us = ws[-1] if ws.size else 0
+        window_start_us = int(window_start_us)
+        cfg, keep = _lib.geojson_cfg(when(window_start_us), when(window_start_us + self.tile_us))
+        pb, po, pr, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        check(self._lib.hm_window_geojson(self._ctx, window_start_us, res, ctypes.byref(cfg), HM_MEM_HOST, ctypes.byref(pb),
+                                          ctypes.byref(po), ctypes.byref(n), ctypes.byref(pr) if with_records else None),
+              self._ctx, "hm_window_geojson")
+        body = self._geojson_body(pb, po, n.value, copy)
+        if not with_records:
+            return body
+        recs = np.zeros(0, STATE_REC_DTYPE)
+        if n.value:
+            recs = np.ctypeslib.as_array(ctypes.cast(pr, ctypes.POINTER(ctypes.c_uint8)),
+                                         shape=(n.value * STATE_REC_DTYPE.itemsize,)).view(STATE_REC_DTYPE).copy()
+        offs = np.ctypeslib.as_array(ctypes.cast(po, ctypes.POINTER(ctypes.c_int64)), shape=(n.value + 1,)).copy()
+        return body, recs, offs
+
+    def encode_tile_features(self, recs, window_start_text, window_end_text, memory=HM_MEM_HOST):
+        """hm_encode_tile_features of STATE_REC_DTYPE records (host memory) with the two window texts: (body bytes,
+        offsets int64[n+1]).  memory=HM_MEM_DEVICE leaves the output on the device and copies it back from there (tests)."""
+        recs = np.ascontiguousarray(recs, dtype=STATE_REC_DTYPE)
+        cfg, keep = _lib.geojson_cfg(window_start_text, window_end_text)
+        pb, po = ctypes.c_void_p(), ctypes.c_void_p()
+        check(self._lib.hm_encode_tile_features(self._ctx, ctypes.byref(cfg), recs.size, HM_MEM_HOST,
+                                                ptr(recs) if recs.size else None, int(memory), ctypes.byref(pb),
+                                                ctypes.byref(po)), self._ctx, "hm_encode_tile_features")
+        n = recs.size
+        if memory == HM_MEM_DEVICE:
+            offs = np.zeros(n + 1, np.int64)
+            check(self._lib.hm_memcpy(ptr(offs), po, offs.nbytes, 1), None, "hm_memcpy")
+            body = np.zeros(_lib.geojson_body_len(offs), np.uint8)
+            check(self._lib.hm_memcpy(ptr(body), pb, body.nbytes, 1), None, "hm_memcpy")
+            return body.tobytes(), offs
+        offs = np.ctypeslib.as_array(ctypes.cast(po, ctypes.POINTER(ctypes.c_int64)), shape=(n + 1,)).copy()
+        return self._geojson_body(pb, po, n, True), offs
+
+    def positions_buckets(self):
+        """The distinct 900-s buckets floor(ts_s / 900) of the positions state's timestamps, ascending (found on the GPU)."""
+        n = ctypes.c_int64()
+        check(self._lib.hm_positions_buckets(self._ctx, None, 0, ctypes.byref(n)), self._ctx, "hm_positions_buckets")
+        ids = np.zeros(n.value, np.int64)
+        if n.value:
+            check(self._lib.hm_positions_buckets(self._ctx, ptr(ids), ids.size, ctypes.byref(n)), self._ctx, "hm_positions_buckets")
+        return ids
+
+    def positions_geojson(self, tz=None, copy=True, with_records=False):
+        """The body of /api/positions/latest: json.dumps(readside.positions_latest_from_engine(...), separators=(",", ":"))
+        as bytes, encoded on the GPU from the positions state.  ts is the naive local datetime the sink writes, or zone
+        tz's wall time (readside.position_docs_from_engine's convention).  copy / with_records as window_geojson."""
+        cfg, keep = _lib.bucket_cfg(self.positions_buckets(), tz)
+        pb, po, pr, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        check(self._lib.hm_positions_geojson(self._ctx, ctypes.byref(cfg), HM_MEM_HOST, ctypes.byref(pb), ctypes.byref(po),
+                                             ctypes.byref(n), ctypes.byref(pr) if with_records else None),
+              self._ctx, "hm_positions_geojson")
+        body = self._geojson_body(pb, po, n.value, copy)
+        if not with_records:
+            return body
+        recs = np.zeros(0, _lib.POSITION_REC_DTYPE)
+        if n.value:
+            recs = np.ctypeslib.as_array(ctypes.cast(pr, ctypes.POINTER(ctypes.c_uint8)),
+                                         shape=(n.value * _lib.POSITION_REC_DTYPE.itemsize,)).view(_lib.POSITION_REC_DTYPE).copy()
+        offs = np.ctypeslib.as_array(ctypes.cast(po, ctypes.POINTER(ctypes.c_int64)), shape=(n.value + 1,)).copy()
+        return body, recs, offs
+
+    def geojson_info(self):
+        v = (ctypes.c_int64 * 4)()
+        check(self._lib.hm_geojson_info(self._ctx, v, 4), self._ctx, "hm_geojson_info")
+        return {"sizes_kernel_us": v[0], "write_kernel_us": v[1], "device_us": v[2], "body_bytes": v[3]}
+
     def _export_buffer(self, n, reuse, raw_out=None):
         """n state records of host memory: a fresh array, or (reuse) a view of the engine's page-locked export buffer --
         valid until the next reuse export (a device-to-host copy into pageable memory ran at ~10 GB/s: 66 ms of a

@@ -132,3 +132,16 @@ def positions_latest_from_engine(engine, tz=None):
     """The FeatureCollection api_positions_latest returns (reference app.py:71-88), from the engine's positions state
     (HeatmapEngine.update_positions after each batch) -- no MongoDB in between."""
     return positions_latest_collection(position_docs_from_engine(engine, tz))
+
+
+def tiles_latest_body(engine, res=None, tz=None):
+    """The response body of api_tiles_latest as bytes: json.dumps(tiles_latest_from_engine(engine, res, tz=tz),
+    separators=(",", ":")), rolled up and encoded on the GPU in one call (HeatmapEngine.window_geojson).  The dict-building
+    functions above stay as the comparison form, as stream.tile_ops is for the sink."""
+    return engine.window_geojson(None, res, tz)
+
+
+def positions_latest_body(engine, tz=None):
+    """The response body of api_positions_latest as bytes: json.dumps(positions_latest_from_engine(engine, tz),
+    separators=(",", ":")), encoded on the GPU from the positions state (HeatmapEngine.positions_geojson)."""
+    return engine.positions_geojson(tz)
