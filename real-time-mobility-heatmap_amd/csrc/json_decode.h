@@ -637,36 +637,42 @@ HM_HD void parse_record(const uint8_t *bytes, int64_t start, int64_t end, uint8_
         r.lat = r.lon = r.speed = __builtin_nan("");
         return;
     }
-    if (f & JF_TS) {   // to_timestamp: the decoded ts string (<= 64 bytes; longer strings are never valid)
+    if (f & JF_TS) {
+        // to_timestamp: the decoded ts string without the blanks around it (to_timestamp trims them, however many);
+        // the longest timestamp is 35 bytes, so more than 64 bytes from its first non-blank one on, other than
+        // trailing blanks, are never valid
         uint8_t tb[64];
         int n = 0;
-        bool ok = ts_span.len <= 64;
-        if (ok) {
-            if (!ts_span.esc) {
-                for (int k = 0; k < ts_span.len; k++) tb[n++] = (uint8_t)R.at(ts_span.start + k);
-            } else {
-                // re-decode the escaped string into tb (escapes in a timestamp: rare)
-                ByteReader R2{bytes, end};
-                int64_t q = ts_span.start;
-                while (n < 64) {
-                    const int c = R2.at(q);
-                    if (c == '"' || c < 0) break;
-                    if (c == '\\') {
-                        const int e = R2.at(q + 1);
-                        if (e == 'u') {
-                            int u = 0;
-                            for (int k = 0; k < 4; k++) u = u * 16 + hexval(R2.at(q + 2 + k));
-                            if (u >= 0x80) { ok = false; break; }   // non-ASCII: not a timestamp
-                            tb[n++] = (uint8_t)u;
-                            q += 6;
-                        } else {
-                            tb[n++] = (uint8_t)(e == 'n' ? 10 : e == 't' ? 9 : e == 'r' ? 13 : e == 'b' ? 8 : e == 'f' ? 12 : e);
-                            q += 2;
-                        }
+        bool ok = true;
+        auto put = [&](int c) {
+            if (n == 0 && c <= ' ') return;          // a leading blank (parse_ts's own trim: bytes <= ' ')
+            if (n < 64) tb[n++] = (uint8_t)c;
+            else if (c > ' ') ok = false;            // (blanks past the buffer can only be trailing ones, or ok is false)
+        };
+        if (!ts_span.esc) {
+            for (int k = 0; k < ts_span.len && ok; k++) put(R.at(ts_span.start + k));
+        } else {
+            // re-decode the escaped string into tb (escapes in a timestamp: rare)
+            ByteReader R2{bytes, end};
+            int64_t q = ts_span.start;
+            while (ok) {
+                const int c = R2.at(q);
+                if (c == '"' || c < 0) break;
+                if (c == '\\') {
+                    const int e = R2.at(q + 1);
+                    if (e == 'u') {
+                        int u = 0;
+                        for (int k = 0; k < 4; k++) u = u * 16 + hexval(R2.at(q + 2 + k));
+                        if (u >= 0x80) { ok = false; break; }   // non-ASCII: not a timestamp
+                        put(u);
+                        q += 6;
                     } else {
-                        tb[n++] = (uint8_t)c;
-                        q++;
+                        put(e == 'n' ? 10 : e == 't' ? 9 : e == 'r' ? 13 : e == 'b' ? 8 : e == 'f' ? 12 : e);
+                        q += 2;
                     }
+                } else {
+                    put(c);
+                    q++;
                 }
             }
         }
