@@ -591,7 +591,9 @@ int hm_selftest_float_repr_device(const double *x, int64_t n, uint8_t *text, int
  * [7] frees the context made since hm_create (steady-state batches make none: tests/test_gpu_parity.py), [8] 1 if the
  * direct path's rows were binned by the ingest itself (no separate partition pass), [9] stage API: of [5], the records
  * of bins this rank owns, kept in its slabs (hm_stage_sizes.n_self_records), [10] hm_process_batch: the chunks the
- * batch was pipelined in (each chunk's ingest overlapping the previous chunk's merge; 0: not pipelined). */
+ * batch was pipelined in (each chunk's ingest overlapping the previous chunk's merge; 0: not pipelined), [11]
+ * hm_process_batch: records of a binned batch that the ingest's producer waves stored themselves because their ring to
+ * the writer waves stayed full (0 on the other paths). */
 int hm_last_counts(const hm_ctx *ctx, int64_t *c, int32_t n);
 /* Version of the persistent tile state: incremented when a batch starts merging into it (hm_process_batch,
  * hm_stage_merge, growth).  A call that failed without changing it left the state as it was (-1: ctx NULL). */

@@ -68,10 +68,26 @@ int hm_create(const hm_config *cfg, hm_ctx **out) {
     for (auto &e : ctx->ev)
         if (hipEventCreate(&e) != hipSuccess) { ctx->err = "event"; return fail("create"); }
     if (upload_tables() != hipSuccess) { ctx->err = "tables"; return fail("create"); }
+    // MOBHEAT_INGEST_WRITERS=0: the binned ingest's fused kernel (every wave stores its own records) instead of the one
+    // with writer waves (k_ingest.h), so that one build times both; MOBHEAT_TEST_RING_POLLS (tests: 0) bounds a
+    // producer wave's wait for room in its ring, after which it stores its round itself
+    ctx->ingest_writers = true;
+    ctx->ring_polls = IGW_RING_POLLS;
+    if (const char *m = getenv("MOBHEAT_INGEST_WRITERS")) ctx->ingest_writers = strcmp(m, "0") != 0;
+    if (const char *m = getenv("MOBHEAT_TEST_RING_POLLS")) ctx->ring_polls = (unsigned)std::max(0, atoi(m));
+    // MOBHEAT_TEST_RING_CAP (tests): the records a ring is taken to hold -- 0: every round finds its ring full, so with
+    // no polls every record takes the producers' own stores; MOBHEAT_TEST_INGEST_GRID (tests): at most that many
+    // workgroups per ingest launch, so that a few thousand rows are many rounds of one workgroup's waves
+    ctx->ring_cap = IGW_RING;
+    if (const char *m = getenv("MOBHEAT_TEST_RING_CAP")) ctx->ring_cap = (unsigned)std::max(0, std::min(atoi(m), IGW_RING));
     for (int variant = 0; variant < 2; variant++) {
-        const void *kern = variant ? (const void *)k_ingest<true> : (const void *)k_ingest<false>;
+        const bool wr = variant && ctx->ingest_writers;
+        const void *kern = wr        ? (const void *)k_ingest<true, false, IGW_WRITERS, IGW_ROUNDS, IGW_PROD>
+                           : variant ? (const void *)k_ingest<true>
+                                     : (const void *)k_ingest<false>;
+        const int threads = wr ? (IGW_PROD + IGW_WRITERS) * 64 : IG_THREADS;
         int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, IG_THREADS, 0) != hipSuccess ||
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, 0) != hipSuccess ||
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) {
             ctx->err = "occupancy query";
             return fail("create");
@@ -82,23 +98,32 @@ int hm_create(const hm_config *cfg, hm_ctx **out) {
         hipFuncAttributes fa{};
         if (hipFuncGetAttributes(&fa, kern) == hipSuccess && fa.sharedSizeBytes > 0)
             per_cu = std::min<int>(per_cu, (int)(163840 / fa.sharedSizeBytes));
-        // k_ingest<true> (the binned ingest) runs 2 workgroups per CU, not the 6 that fit: its time is its records'
-        // scattered stores and bin-cursor atomics, which fewer waves in flight contend less for -- 5.41-5.50 ms at 2
-        // against 5.62-5.67 at 3 and 5.88-5.97 at 6 (profiles/r5/r5wg2/, r5wg3/; 1 per CU: ~7 ms); the unbinned
-        // kernel keeps every resident block (VALU and latency bound).  MOBHEAT_INGEST_WG_PER_CU overrides (tuning)
+        // the binned ingest runs 2 workgroups per CU.  Its fused kernel's time is its records' scattered stores and
+        // bin-cursor atomics, which fewer waves in flight contend less for -- 5.41-5.50 ms at 2 against 5.62-5.67 at 3
+        // and 5.88-5.97 at 6 (profiles/r5/r5wg2/, r5wg3/; 1 per CU: ~7 ms) -- but 8 waves per CU starve the cell
+        // computation of the occupancy that hides its latency.  The kernel with writer waves separates the two: 16
+        // producer waves per CU compute cells, 4 writer waves per CU (16 rounds of cursor atomics in flight) store, and
+        // the ingest takes 4.2-4.4 ms where the fused kernel took 4.9 on the same box (DESIGN section 7,
+        // profiles/r7/) -- from the times alone (no wait counters were read), what cost was the number of waves at
+        // the cursors and slabs, not the number resident.  The
+        // unbinned kernel keeps every resident block (VALU and latency bound).  MOBHEAT_INGEST_WG_PER_CU overrides (tuning)
         if (variant) per_cu = std::min(per_cu, 2);
         if (const char *m = getenv("MOBHEAT_INGEST_WG_PER_CU")) {
             int w = 0, cap = 0;
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&cap, kern, IG_THREADS, 0);
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&cap, kern, threads, 0);
             if (fa.sharedSizeBytes > 0) cap = std::min<int>(cap, (int)(163840 / fa.sharedSizeBytes));
             w = atoi(m);
             if (w > 0) per_cu = std::max(1, std::min(cap, w));
         }
         if (getenv("MOBHEAT_DEBUG"))
-            fprintf(stderr, "mobheat: k_ingest<%d> %d blocks/CU x %d CUs (LDS %zu B, %d VGPRs)\n", variant, per_cu, cus,
-                    fa.sharedSizeBytes, fa.numRegs);
+            fprintf(stderr, "mobheat: k_ingest<%d>%s %d blocks/CU of %d threads x %d CUs (LDS %zu B, %d VGPRs)\n", variant,
+                    wr ? " (writer waves)" : "", per_cu, threads, cus, fa.sharedSizeBytes, fa.numRegs);
         (variant ? ctx->ingest_grid_bin : ctx->ingest_grid) = std::max(1, per_cu) * std::max(1, cus);
         ctx->n_cus = std::max(1, cus);
+    }
+    if (const char *m = getenv("MOBHEAT_TEST_INGEST_GRID")) {
+        const int g = atoi(m);
+        if (g > 0) { ctx->ingest_grid = std::min(ctx->ingest_grid, g); ctx->ingest_grid_bin = std::min(ctx->ingest_grid_bin, g); }
     }
     // MOBHEAT_INGEST_MODE=direct|table|binned pins the aggregation path (tests): the direct path with its partition
     // pass, table mode, or the direct path binned in k_ingest at any batch size; default: adaptive
@@ -284,6 +309,7 @@ int hm_last_counts(const hm_ctx *ctx, int64_t *c, int32_t n) {
     if (n > 8) c[8] = ctx->last_binned;
     if (n > 9) c[9] = ctx->staged ? ctx->stage_self_recs : 0;
     if (n > 10) c[10] = ctx->staged ? 0 : ctx->last_pipe_chunks;
+    if (n > 11) c[11] = ctx->last_ring_direct;
     return HM_OK;
 }
 
@@ -327,6 +353,7 @@ int hm_process_batch(hm_ctx *ctx, int64_t epoch_id, const hm_batch_in *in, int32
         return rc;
     }
     DevStats s1 = *ctx->h_st;
+    ctx->last_ring_direct = (int64_t)s1.ring_direct;
     const int64_t n_agg = (int64_t)s1.n_valid - (int64_t)s1.n_late;
     // the aggregation path of this batch (table mode: two LDS passes first; direct: every row a record)
     const bool table = !piped && choose_table(ctx, n_agg, s1.sample_max_run);

@@ -88,15 +88,19 @@ static int prepare_local(hm_ctx *ctx, int64_t n, int64_t late_wm_ms, bool bin, b
 
 // k_ingest over rows [a, b) of the batch I (bin: k_ingest<true>, the rows' records into their bin slabs)
 static void launch_ingest(hm_ctx *ctx, const Inputs &I, int64_t a, int64_t b, bool bin, int64_t late_wm_ms) {
-    const int blocks = (int)std::min<int64_t>((b - a + IG_THREADS - 1) / IG_THREADS, bin ? ctx->ingest_grid_bin : ctx->ingest_grid);
-    auto kern = bin ? k_ingest<true> : k_ingest<false>;
-    hipLaunchKernelGGL(kern, dim3(std::max(blocks, 1)), dim3(IG_THREADS), 0, ctx->stream, I.lat, I.lon, I.ts, I.rv, I.vk, a, b,
+    // (ctx->ingest_writers: the binned kernel with writer waves, its workgroup IGW_PROD waves of rows + the writers)
+    const bool wr = bin && ctx->ingest_writers;
+    const int rows = wr ? IGW_PROD * 64 : IG_THREADS, threads = wr ? (IGW_PROD + IGW_WRITERS) * 64 : IG_THREADS;
+    const int blocks = (int)std::min<int64_t>((b - a + rows - 1) / rows, bin ? ctx->ingest_grid_bin : ctx->ingest_grid);
+    auto kern = wr ? k_ingest<true, false, IGW_WRITERS, IGW_ROUNDS, IGW_PROD> : bin ? k_ingest<true> : k_ingest<false>;
+    hipLaunchKernelGGL(kern, dim3(std::max(blocks, 1)), dim3(threads), 0, ctx->stream, I.lat, I.lon, I.ts, I.rv, I.vk, a, b,
                        ctx->cfg.h3_res, make_floor_div(ctx->cfg.tile_us), late_wm_ms * 1000, (uint8_t *)ctx->flags.p,
                        (uint64_t *)ctx->keys.p, ctx->dfused.tab, ctx->dfused.cap - 1, (unsigned int *)ctx->dfused.used.p,
                        ctx->d_scratch + ctx->dfused.used_word, (unsigned int *)ctx->slow.p, ctx->d_scratch + SLOW_WORD,
                        ctx->d_scratch + GIVEUP_WORD, ctx->d_wreg, ctx->d_wcount, ctx->d_st, I.sp, I.sv,
                        (unsigned *)ctx->bin_cur.p, bin ? (EventRec *)ctx->parts_sorted.p : nullptr, ctx->slab_cap,
-                       (unsigned long long *)ctx->dense.p, ctx->dense_cap, ctx->sub_bits, hs_stride(I.n) - 1);
+                       (unsigned long long *)ctx->dense.p, ctx->dense_cap, ctx->sub_bits, hs_stride(I.n) - 1, ctx->ring_polls,
+                       ctx->ring_cap);
 }
 
 static int phase_local(hm_ctx *ctx, const Inputs &I, int64_t late_wm_ms, bool allow_bin = false, bool sub = false,
@@ -180,7 +184,7 @@ static int keys_complete(hm_ctx *ctx, const Inputs &I) {
                        (unsigned int *)ctx->dfused.used.p, ctx->d_scratch + ctx->dfused.used_word, (unsigned int *)ctx->slow.p,
                        ctx->d_scratch + SLOW_WORD, ctx->d_scratch + GIVEUP_WORD, ctx->d_wreg, ctx->d_wcount, ctx->d_st, I.sp,
                        I.sv, (unsigned *)ctx->bin_cur.p, (EventRec *)nullptr, 0u, (unsigned long long *)ctx->dense.p, 0ull, 0u,
-                       (int64_t)0);
+                       (int64_t)0, 0u, 0u);
     HIPCHK(ctx, hipGetLastError());
     return HM_OK;
 }

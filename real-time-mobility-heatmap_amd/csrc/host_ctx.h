@@ -103,7 +103,11 @@ struct hm_ctx {
     int64_t dedup_seen = 0;
     int64_t n_partials_merged = 0;   // partial records of the last merge (hm_batch_out.n_partials)
     int ingest_grid = 0;             // k_ingest's persistent grid: resident workgroups per CU x CUs
-    int ingest_grid_bin = 0;         // the same for k_ingest<true> (fused binning)
+    int ingest_grid_bin = 0;         // the same for k_ingest<true> (fused binning), the instantiation ingest_writers picks
+    bool ingest_writers = false;     // the binned ingest's records go through writer waves (MOBHEAT_INGEST_WRITERS)
+    unsigned ring_polls = 0;         // a producer wave's polls of its full ring (MOBHEAT_TEST_RING_POLLS; tests: 0)
+    unsigned ring_cap = 0;           // records a ring is taken to hold, <= IGW_RING (MOBHEAT_TEST_RING_CAP; tests: 0, 64)
+    int64_t last_ring_direct = 0;    // hm_last_counts [11]: records the last batch's producer waves stored themselves
     int64_t last_binned = 0;         // hm_last_counts [8]: the last batch was binned in k_ingest
     int n_cus = 0;
     // aggregation path: direct (event records -> partition -> merge) or table (k_agg + k_bin_reduce, low

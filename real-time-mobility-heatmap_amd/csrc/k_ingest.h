@@ -9,8 +9,10 @@
 // the register footprint of the exact path never limits the occupancy of the streaming kernel.
 // =====================================================================================================
 // waves per SIMD for k_ingest: 6 (<= 80 VGPRs, no spills; 7 or 8 spill and only lengthen the waits, profiles/r3/r3ab15/,
-// profiles/r4/r4wv/)
-#define HM_SNAP_ATTR __attribute__((amdgpu_waves_per_eu(6)))
+// profiles/r4/r4wv/); with writer waves the kernel takes 95 VGPRs, no spills: 5 waves per SIMD, the 2 workgroups of 10
+// waves a CU runs.  One function for k_ingest's attribute and the macro (tools/diag/ingest_phases.hip's kernels)
+constexpr int ig_waves_per_simd(int writers) { return writers ? 5 : 6; }
+#define HM_SNAP_ATTR __attribute__((amdgpu_waves_per_eu(ig_waves_per_simd(0))))
 // standalone UDF: cells only (hm_latlng_to_cell); exceptions -> slow[]
 __global__ __launch_bounds__(256) void k_cells(const double *__restrict__ lat, const double *__restrict__ lon, int64_t n,
                                                int res, uint64_t *__restrict__ out, unsigned int *__restrict__ slow,
@@ -92,8 +94,101 @@ __host__ __device__ inline int64_t hs_stride(int64_t n) {
 // needs every row's key (the key sample asks for table mode, or a slab overflowed and the batch re-partitions) runs
 // kKeys: the same rows again, writing only the keys of the non-exception rows (no flags, dedup, census, statistics,
 // bins), so that the keys read as one k_ingest<false> would have written them (keys_complete).
-template <bool kBin, bool kKeys = false>
-__global__ __launch_bounds__(IG_THREADS) HM_SNAP_ATTR void k_ingest(
+// kWriters > 0 (kBin only): the workgroup is kProd producer waves, which run the rows as above, and kWriters writer
+// waves, which alone touch the bin cursors and slabs.  A producer wave appends its round's records, compacted, to its
+// own LDS ring (single producer, single consumer: tail is the producer's word, head the writer's; counts of records,
+// slot = count mod IGW_RING); writer j drains the rings of producers j, j + kWriters, ... a full wave of records at a
+// time (a ring's last records once its producer is done), kRounds rounds of cursor atomics in flight before the first
+// is waited for.  Nothing waits without bound: a producer that finds its ring full polls ring_polls times and then
+// stores its round itself (the fused kernel's path; counted in DevStats.ring_direct), and a writer leaves when its
+// producers are done and their rings empty -- which the producers' own loop bounds bring about.
+constexpr int IGW_RING = 128;              // records per ring: two full rounds
+constexpr int IGW_PROD = 8;                // producer waves per workgroup
+constexpr int IGW_WRITERS = 2, IGW_ROUNDS = 4;   // writer waves per workgroup, rounds of cursor atomics in flight in each
+constexpr unsigned IGW_RING_POLLS = 256;   // a producer's polls of a full ring before it stores its round itself
+struct IngestRing {
+    unsigned long long key[IGW_RING], sp[IGW_RING], la[IGW_RING], lo[IGW_RING];   // (the EventRec's words)
+    unsigned bin[IGW_RING];
+    unsigned tail, head, done;
+};
+template <int kProd>
+struct IngestRings { IngestRing r[kProd]; };
+template <>
+struct IngestRings<0> {};
+__device__ __forceinline__ unsigned ring_word(const unsigned *w) {   // (one LDS word, the same in every lane)
+    return __builtin_amdgcn_readfirstlane(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+}
+// (fences of the LDS alone: they wait for the wave's LDS operations, not for its loads in flight)
+__device__ __forceinline__ void ring_acquire() { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local"); }
+__device__ __forceinline__ void ring_publish(unsigned *w, unsigned v) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    if (lane_id() == 0) __hip_atomic_store(w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+// writer wave wj of kWriters; returns this lane's count of records whose slab was full
+template <int kProd, int kWriters, int kRounds>
+__device__ __forceinline__ unsigned ingest_writer(IngestRings<kProd> &RG, int wj, unsigned *__restrict__ bin_cur,
+                                                  EventRec *__restrict__ slabs, unsigned slab_cap) {
+    constexpr int NQ = (kProd + kWriters - 1) / kWriters;   // rings of one writer, at most
+    const unsigned ln = (unsigned)lane_id();
+    unsigned over = 0;
+    int cur = wj;   // the next ring to look at
+    for (;;) {
+        unsigned cnt[kRounds], b[kRounds], p[kRounds];
+        uint64_t key[kRounds], sp[kRounds], la[kRounds], lo[kRounds];
+#pragma unroll
+        for (int r = 0; r < kRounds; r++) {
+            cnt[r] = 0;
+            b[r] = p[r] = 0;
+            key[r] = sp[r] = la[r] = lo[r] = 0;
+            for (int tries = 0; tries < NQ && cnt[r] == 0; tries++) {
+                IngestRing &Q = RG.r[cur];
+                cur = cur + kWriters < kProd ? cur + kWriters : wj;
+                const unsigned d = ring_word(&Q.done);
+                ring_acquire();   // (done is read before tail: a done producer's tail is final)
+                const unsigned t = ring_word(&Q.tail), h = ring_word(&Q.head);
+                ring_acquire();
+                const unsigned avail = t - h, take = avail >= 64 ? 64u : d ? avail : 0u;
+                if (take == 0) continue;
+                if (ln < take) {
+                    const unsigned s = (h + ln) & (IGW_RING - 1);
+                    b[r] = Q.bin[s];
+                    key[r] = Q.key[s];
+                    sp[r] = Q.sp[s];
+                    la[r] = Q.la[s];
+                    lo[r] = Q.lo[s];
+                }
+                ring_publish(&Q.head, h + take);   // (the records are in registers: the slots are free again)
+                cnt[r] = take;
+            }
+            if (ln < cnt[r]) p[r] = atomicAdd(&bin_cur[b[r]], 1u);
+        }
+#pragma unroll
+        for (int r = 0; r < kRounds; r++) {
+            if (ln >= cnt[r]) continue;
+            if (p[r] < slab_cap) {
+                uint4 *d = (uint4 *)&slabs[(size_t)b[r] * slab_cap + p[r]];
+                st_g16(d, make_uint4((unsigned)key[r], (unsigned)(key[r] >> 32), (unsigned)sp[r], (unsigned)(sp[r] >> 32)));
+                st_g16(d + 1, make_uint4((unsigned)la[r], (unsigned)(la[r] >> 32), (unsigned)lo[r], (unsigned)(lo[r] >> 32)));
+            } else {
+                over++;
+            }
+        }
+        if (cnt[0]) continue;
+        // the first round looked at every ring and found none ready: done, or wait for the producers
+        bool fin = true;
+        for (int q = wj; q < kProd; q += kWriters) {
+            const unsigned d = ring_word(&RG.r[q].done);
+            ring_acquire();
+            fin = fin && d && ring_word(&RG.r[q].tail) == ring_word(&RG.r[q].head);
+        }
+        if (fin) break;
+        __builtin_amdgcn_s_sleep(8);
+    }
+    return over;
+}
+
+template <bool kBin, bool kKeys = false, int kWriters = 0, int kRounds = 1, int kProd = IG_THREADS / 64>
+__global__ __launch_bounds__((kProd + kWriters) * 64) __attribute__((amdgpu_waves_per_eu(ig_waves_per_simd(kWriters)))) void k_ingest(
     const double *__restrict__ lat, const double *__restrict__ lon, const int64_t *__restrict__ ts,
     const uint8_t *__restrict__ row_valid, const uint64_t *__restrict__ vkey, int64_t i_begin, int64_t n, int res_arg, FloorDiv wdiv,
     int64_t late_end_us, uint8_t *__restrict__ flags_out, uint64_t *__restrict__ keys_out, DedupSlot *dtab,
@@ -101,23 +196,32 @@ __global__ __launch_bounds__(IG_THREADS) HM_SNAP_ATTR void k_ingest(
     unsigned long long *n_slow, unsigned long long *dgiveup, unsigned long long *wreg, unsigned long long *wcount,
     DevStats *st, const double *__restrict__ speed, const uint8_t *__restrict__ speed_valid, unsigned *__restrict__ bin_cur,
     EventRec *__restrict__ slabs, unsigned slab_cap, unsigned long long *__restrict__ dense, unsigned long long dense_cap,
-    unsigned sub_bits, int64_t smask) {
+    unsigned sub_bits, int64_t smask, unsigned ring_polls, unsigned ring_cap) {
     static_assert(!(kBin && kKeys), "k_ingest: kKeys runs unbinned");
+    static_assert(kWriters == 0 ? kProd * 64 == IG_THREADS : kBin, "k_ingest: writer waves belong to the binned kernel");
+    constexpr int kRows = kProd * 64, kThreads = (kProd + kWriters) * 64;   // a round's rows; the workgroup
+    // (the wave's number as a scalar: the row loop's bounds stay wave-uniform for the compiler)
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const bool writer = kWriters > 0 && wave >= kProd;
+    __shared__ IngestRings<kWriters ? kProd : 0> RG;
+    if constexpr (kWriters > 0)
+        if (threadIdx.x < kProd) RG.r[threadIdx.x].tail = RG.r[threadIdx.x].head = RG.r[threadIdx.x].done = 0;
+    unsigned ring_tail = 0;   // this producer wave's records so far
     const int res = res_arg;
     __shared__ WinCacheL WC;
     __shared__ double Fc[20][3], Fu[20][2][3];   // the fast path's per-face tables (res parity): LDS reads
     __shared__ unsigned dskip;                    // the fused dedup has given up (*dgiveup) -- skip it
-    __shared__ long long tmax_l[IG_THREADS];      // per-thread max ts (an LDS max per row instead of 2 live registers)
-    __shared__ long long vmax_l[IG_THREADS];      // per-thread max vkey + 1 of the deduplicated rows (the same way)
-    for (int k = threadIdx.x; k < 60; k += IG_THREADS) (&Fc[0][0])[k] = (&c_tab.faceCenterPoint[0][0])[k];
-    for (int k = threadIdx.x; k < 120; k += IG_THREADS) (&Fu[0][0][0])[k] = (&c_tab.fastU[res & 1][0][0][0])[k];
+    __shared__ long long tmax_l[kThreads];        // per-thread max ts (an LDS max per row instead of 2 live registers)
+    __shared__ long long vmax_l[kThreads];        // per-thread max vkey + 1 of the deduplicated rows (the same way)
+    for (int k = threadIdx.x; k < 60; k += kThreads) (&Fc[0][0])[k] = (&c_tab.faceCenterPoint[0][0])[k];
+    for (int k = threadIdx.x; k < 120; k += kThreads) (&Fu[0][0][0])[k] = (&c_tab.fastU[res & 1][0][0][0])[k];
     // _faceIjkToH3's packed base-cell and digit tables in LDS (11.2 KB): from __constant__ memory they were lane-indexed vector loads
     // at the end of every cell, each with a full wait that also waited for the next round's prefetched columns
     __shared__ H3BaseTables BT;
-    for (int k = threadIdx.x; k < 20 * 27; k += IG_THREADS) BT.fijkPacked[k] = c_tab.fijkPacked[k];
-    for (int k = threadIdx.x; k < 122; k += IG_THREADS) BT.bcdPacked[k] = c_tab.bcdPacked[k];
-    for (int k = threadIdx.x; k < AP7_QUAD; k += IG_THREADS) BT.ap7Quad[k] = c_tab.ap7Quad[k];
-    for (int k = threadIdx.x; k < AP7_PAIR; k += IG_THREADS) BT.ap7Pair[k] = c_tab.ap7Pair[k];
+    for (int k = threadIdx.x; k < 20 * 27; k += kThreads) BT.fijkPacked[k] = c_tab.fijkPacked[k];
+    for (int k = threadIdx.x; k < 122; k += kThreads) BT.bcdPacked[k] = c_tab.bcdPacked[k];
+    for (int k = threadIdx.x; k < AP7_QUAD; k += kThreads) BT.ap7Quad[k] = c_tab.ap7Quad[k];
+    for (int k = threadIdx.x; k < AP7_PAIR; k += kThreads) BT.ap7Pair[k] = c_tab.ap7Pair[k];
     wc_init(WC);
     if (threadIdx.x == 0) dskip = 0;
     __syncthreads();
@@ -129,7 +233,7 @@ __global__ __launch_bounds__(IG_THREADS) HM_SNAP_ATTR void k_ingest(
     vmax_l[threadIdx.x] = 0;
     bool dretry = false;
     int round = 0;
-    const int64_t gstride = (int64_t)gridDim.x * IG_THREADS;
+    const int64_t gstride = (int64_t)gridDim.x * kRows;
     // the next round's columns are loaded while this round computes its cells (software pipelining: the loads'
     // latency hides behind the fp64 work instead of stalling every round)
     double nla = 0.0, nlo = 0.0;
@@ -137,15 +241,16 @@ __global__ __launch_bounds__(IG_THREADS) HM_SNAP_ATTR void k_ingest(
     unsigned long long nv = EMPTY_VKEY;
     uint8_t nrv = 1;
     {
-        const int64_t i0 = i_begin + (int64_t)blockIdx.x * IG_THREADS + threadIdx.x;
-        if (i0 < n) {
+        const int64_t i0 = i_begin + (int64_t)blockIdx.x * kRows + threadIdx.x;
+        if (i0 < n && !writer) {
             nla = __builtin_nontemporal_load(&lat[i0]);
             nlo = __builtin_nontemporal_load(&lon[i0]);
             nv = __builtin_nontemporal_load(&vkey[i0]);
             if (row_valid) nrv = __builtin_nontemporal_load(&row_valid[i0]);
         }
     }
-    for (int64_t base = i_begin + (int64_t)blockIdx.x * IG_THREADS; base < n; base += gstride, round++) {
+    // (a writer wave runs no rows: it drains its producers' rings, below the loop)
+    for (int64_t base = writer ? n : i_begin + (int64_t)blockIdx.x * kRows; base < n; base += gstride, round++) {
         const int64_t i = base + threadIdx.x;
         const bool in = i < n;
         const double la = nla, lo = nlo;
@@ -248,7 +353,9 @@ __global__ __launch_bounds__(IG_THREADS) HM_SNAP_ATTR void k_ingest(
         }
         if constexpr (kBin) {
             // the row's EventRec into its bin (exceptions: k_ingest_exact, once their cell is known)
-            if (agg && !exc) {
+            const bool rec = agg && !exc;
+            unsigned b = 0;
+            if (rec) {
                 // the window's hash constant from the window cache (computed by the first rows that find it unset:
                 // every writer stores the same value)
                 uint64_t inner = wslot >= 0 ? __hip_atomic_load(&WC.inner[wslot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0;
@@ -257,12 +364,45 @@ __global__ __launch_bounds__(IG_THREADS) HM_SNAP_ATTR void k_ingest(
                     if (wslot >= 0) __hip_atomic_store(&WC.inner[wslot], inner, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
                 const uint64_t h = mix64(cell ^ inner);
-                const unsigned b = (region_field(h) << sub_bits) | (sub_field(h) & ((1u << sub_bits) - 1));
+                b = (region_field(h) << sub_bits) | (sub_field(h) & ((1u << sub_bits) - 1));
+            }
+            const uint64_t sp = svb == 0 ? SPEED_NULL_BITS
+                                         : __builtin_bit_cast(double, spb) != __builtin_bit_cast(double, spb) ? CANON_NAN_BITS : spb;
+            const uint64_t lab = __builtin_bit_cast(uint64_t, la), lob = __builtin_bit_cast(uint64_t, lo);
+            bool direct = rec;   // this lane stores its record itself
+            if constexpr (kWriters > 0) {
+                // the round's records, compacted, into this wave's ring when it has room for them
+                const unsigned long long m = __ballot(rec);
+                if (m) {
+                    IngestRing &Q = RG.r[wave];
+                    const unsigned cnt = (unsigned)__popcll(m);
+                    // (ring_cap <= IGW_RING: the records the ring is taken to hold -- tests make it small or 0)
+                    bool room = ring_tail + cnt - ring_word(&Q.head) <= ring_cap;
+                    for (unsigned q = 0; !room && q < ring_polls; q++) {
+                        __builtin_amdgcn_s_sleep(4);
+                        room = ring_tail + cnt - ring_word(&Q.head) <= ring_cap;
+                    }
+                    if (room) {
+                        ring_acquire();   // (the writer has read the slots it freed)
+                        if (rec) {
+                            const unsigned s = (ring_tail + (unsigned)__popcll(m & ((1ull << lane_id()) - 1))) & (IGW_RING - 1);
+                            Q.bin[s] = b;
+                            Q.key[s] = key;
+                            Q.sp[s] = sp;
+                            Q.la[s] = lab;
+                            Q.lo[s] = lob;
+                        }
+                        ring_tail += cnt;
+                        ring_publish(&Q.tail, ring_tail);
+                        direct = false;
+                    } else if (lane_id() == 0) {
+                        atomicAdd(&st->ring_direct, (unsigned long long)cnt);   // (rare: the ring stayed full)
+                    }
+                }
+            }
+            if (direct) {
                 const unsigned p = atomicAdd(&bin_cur[b], 1u);
                 if (p < slab_cap) {
-                    const uint64_t sp = svb == 0 ? SPEED_NULL_BITS
-                                                 : __builtin_bit_cast(double, spb) != __builtin_bit_cast(double, spb) ? CANON_NAN_BITS : spb;
-                    const uint64_t lab = __builtin_bit_cast(uint64_t, la), lob = __builtin_bit_cast(uint64_t, lo);
                     uint4 *d = (uint4 *)&slabs[(size_t)b * slab_cap + p];
                     st_g16(d, make_uint4((unsigned)key, (unsigned)(key >> 32), (unsigned)sp, (unsigned)(sp >> 32)));
                     st_g16(d + 1, make_uint4((unsigned)lab, (unsigned)(lab >> 32), (unsigned)lob, (unsigned)(lob >> 32)));
@@ -284,8 +424,12 @@ __global__ __launch_bounds__(IG_THREADS) HM_SNAP_ATTR void k_ingest(
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     if constexpr (kKeys) return;   // (no census, no statistics: the batch's first pass counted them)
+    if constexpr (kWriters > 0) {
+        if (writer) binover = ingest_writer<kProd, kWriters, kRounds>(RG, wave - kProd, bin_cur, slabs, slab_cap);
+        else ring_publish(&RG.r[wave].done, 1u);   // (after the wave's last tail)
+    }
     __syncthreads();
-    for (int q = threadIdx.x; q < WC_SLOTS; q += IG_THREADS)
+    for (int q = threadIdx.x; q < WC_SLOTS; q += kThreads)
         if (WC.cnt[q]) atomicAdd(&wcount[(WC.e[q] & 0xfff) - 1], (unsigned long long)WC.cnt[q]);
     const unsigned long long wvalid = wave_sum((unsigned long long)nvalid), wlate = wave_sum((unsigned long long)nlate);
     const unsigned long long wbad = wave_sum((unsigned long long)bad), wwover = wave_sum((unsigned long long)wover);

@@ -202,6 +202,8 @@ struct DevStats {
     unsigned long long bin_overflow;     // k_ingest<true>: rows whose bin slab was full (the batch re-partitions)
     unsigned long long vkey_max1;        // k_ingest: max vkey + 1 of its deduplicated rows (capped at 2^62; sizes the
                                          // next batch's dense dedup table)
+    unsigned long long ring_direct;      // k_ingest with writer waves: records a producer wave stored itself, its ring
+                                         // full (hm_last_counts [11])
 };
 
 // the dense dedup table's word: a max ts with its sign bit flipped (k_ingest.h: unsigned order = signed order, 0 = none)
