@@ -833,6 +833,9 @@ static int winfo_upload(hm_ctx *ctx, bool with_bins) {
             bool found = false;
             for (const auto &g : ctx->gens)
                 if (g.wenc == we) { sb = g.sb; found = true; break; }
+            // (a stage owner's registry is the batch's global one: a window none of whose records this rank received
+            // -- every key of it is another rank's -- has no table here and no record that looks its entry up)
+            if (!found && ctx->staged && !ctx->h_wcount[w]) continue;
             if (!found) return set_err(ctx, HM_E_STATE, "window without a state table");
             x.binp = (sb << 24) | (window_salt(we) & ((1u << sb) - 1));
         }

@@ -96,12 +96,13 @@ def _u8(a, n):
 class HeatmapEngine:
     def __init__(self, h3_res=8, tile_minutes=5, watermark_delay_ms=600_000, device=0,
                  late_uses_prev_watermark=True, state_capacity_hint=0, batch_capacity_hint=0, state_arena_bytes=0,
-                 shard=None):
+                 shard=None, tile_us=None):
         """shard: (rank, world) of a multi-GPU stage context (its state holds only the keys that rank owns); None =
-        fixed by the first hm_stage_ingest, or a single GPU."""
+        fixed by the first hm_stage_ingest, or a single GPU.  tile_us: the window length in microseconds, overriding
+        tile_minutes (hm_create takes any tile_us >= 1 000 000)."""
         self._lib = _lib.load()
         self.h3_res = int(h3_res)
-        self.tile_us = int(tile_minutes) * 60 * 1_000_000
+        self.tile_us = int(tile_us) if tile_us is not None else int(tile_minutes) * 60 * 1_000_000
         self.device = int(device)
         cfg = HmConfig(abi_version=_lib.HM_ABI_VERSION, h3_res=self.h3_res, device=self.device,
                        late_uses_prev_watermark=1 if late_uses_prev_watermark else 0, tile_us=self.tile_us,

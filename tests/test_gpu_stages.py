@@ -35,9 +35,10 @@ class DevBuf:
         self.lib.hm_device_free(0, self.p)
 
 
-def _stage_batch(engines, lib, batches_per_rank, epoch):
+def _stage_batch(engines, lib, batches_per_rank, epoch, stats=None):
     """One micro-batch through the stage API of W contexts, exchanges routed on the host.  Returns the owners' tiles,
-    each rank's latest rows, per-rank tile/candidate send counts and whether table mode ran."""
+    each rank's latest rows, per-rank tile/candidate send counts and whether table mode ran.  stats (a list) receives
+    each rank's BatchResult of hm_stage_merge (its statistics and watermarks)."""
     from mobheat._lib import HM_MEM_HOST, HM_STAGE_SUMMARY_WORDS, HmBatchIn, HmBatchOut, HmStageSizes, check
     W = len(engines)
     bufs, keep = [], []
@@ -96,6 +97,8 @@ def _stage_batch(engines, lib, batches_per_rank, epoch):
                                  max(nc, 1), wc), eng._ctx)
         res = eng._result_from_host(out)
         outs.append(res.tiles)
+        if stats is not None:
+            stats.append(res)
         wcounts.append(list(wc))
         wsends.append(wb.get(sum(wc) * 8).view(np.int64))
         c = eng.last_counts()
