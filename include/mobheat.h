@@ -593,7 +593,12 @@ int hm_selftest_float_repr_device(const double *x, int64_t n, uint8_t *text, int
  * of bins this rank owns, kept in its slabs (hm_stage_sizes.n_self_records), [10] hm_process_batch: the chunks the
  * batch was pipelined in (each chunk's ingest overlapping the previous chunk's merge; 0: not pipelined), [11]
  * hm_process_batch: records of a binned batch that the ingest's producer waves stored themselves because their ring to
- * the writer waves stayed full (0 on the other paths). */
+ * the writer waves stayed full (0 on the other paths), [12] the variant of the owner merge kernel at the batch's last
+ * launch of it, a bit set: 1 resident-only (every window's region tags in LDS, no HBM-probing fallback), 2 the
+ * wave-cooperative probe, 4 the bins' records read as segments, 8 at least one record of the batch probed its slot
+ * through HBM (0: the batch merged nothing; a growth's rehash merge is not recorded).  Tests choose the variant with
+ * MOBHEAT_TEST_MERGE_TAGS=<bytes> (at most that much LDS for resident tags; 0: none) and MOBHEAT_TEST_MERGE_COOP=0|1
+ * (the probe of a resident-only merge), read at hm_create. */
 int hm_last_counts(const hm_ctx *ctx, int64_t *c, int32_t n);
 /* Version of the persistent tile state: incremented when a batch starts merging into it (hm_process_batch,
  * hm_stage_merge, growth).  A call that failed without changing it left the state as it was (-1: ctx NULL). */

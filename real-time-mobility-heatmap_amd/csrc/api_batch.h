@@ -53,15 +53,9 @@ int hm_create(const hm_config *cfg, hm_ctx **out) {
     for (auto &e : ctx->stm_ev)
         if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { ctx->err = "event"; return fail("create"); }
     // k_merge_owned's resident tags live in dynamic LDS of up to MO_TAG_MAX bytes (merge_sorted)
-    if (hipFuncSetAttribute((const void *)k_merge_owned<EventRec, false>, hipFuncAttributeMaxDynamicSharedMemorySize, MO_TAG_MAX) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_merge_owned<EventRec, true>, hipFuncAttributeMaxDynamicSharedMemorySize, MO_TAG_MAX) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_merge_owned<EventRec, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, MO_TAG_MAX) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_merge_owned<SortedRec, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, MO_TAG_MAX) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_merge_owned<SortedRec, false>, hipFuncAttributeMaxDynamicSharedMemorySize, MO_TAG_MAX) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_merge_owned<SortedRec, true>, hipFuncAttributeMaxDynamicSharedMemorySize, MO_TAG_MAX) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_merge_owned<EventRec, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, MO_TAG_MAX) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_merge_owned<EventRec, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, MO_TAG_MAX) != hipSuccess ||
-        hipFuncSetAttribute((const void *)k_merge_owned<EventRec, true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, MO_TAG_MAX) != hipSuccess) {
+    if (!for_each_merge_variant([](const void *kern) {
+            return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, MO_TAG_MAX) == hipSuccess;
+        })) {
         ctx->err = "merge LDS attribute";
         return fail("create");
     }
@@ -143,6 +137,12 @@ int hm_create(const hm_config *cfg, hm_ctx **out) {
     // pipelines every binned batch in K chunks (tests, A/B), "auto": batches of >= PIPE_MIN_ROWS rows in PIPE_CHUNKS chunks
     if (const char *m = getenv("MOBHEAT_PIPELINE")) ctx->pipe_mode = !strcmp(m, "auto") ? -1 : std::max(0, std::min(atoi(m), hm_ctx::PIPE_MAX));
     if (const char *m = getenv("MOBHEAT_TEST_SLAB_CAP")) ctx->test_slab_cap = (unsigned)std::max(0, atoi(m));
+    // MOBHEAT_TEST_MERGE_TAGS (tests): at most that many bytes of resident region tags per merge workgroup -- 0: no
+    // region is resident, every record probes through HBM; less than the batch's windows need: the merge with the
+    // HBM-probing fallback, the windows that still fit resident; MOBHEAT_TEST_MERGE_COOP=0|1 (tests): the per-lane or the
+    // cooperative probe of a resident merge, whatever the batch's share of existing keys (merge_sorted)
+    if (const char *m = getenv("MOBHEAT_TEST_MERGE_TAGS")) ctx->test_merge_tags = std::max(0, atoi(m));
+    if (const char *m = getenv("MOBHEAT_TEST_MERGE_COOP")) ctx->test_merge_coop = strcmp(m, "0") != 0;
     // the registry, its census and the batch statistics side by side (one reset, one readback after k_ingest)
     if (hipMalloc(&ctx->d_wreg, REG_BLOCK_BYTES) != hipSuccess || !(ctx->d_wcount = ctx->d_wreg + WREG_SLOTS + 1) ||
         !(ctx->d_st = (DevStats *)(ctx->d_wreg + 2 * (WREG_SLOTS + 1))) ||
@@ -310,6 +310,7 @@ int hm_last_counts(const hm_ctx *ctx, int64_t *c, int32_t n) {
     if (n > 9) c[9] = ctx->staged ? ctx->stage_self_recs : 0;
     if (n > 10) c[10] = ctx->staged ? 0 : ctx->last_pipe_chunks;
     if (n > 11) c[11] = ctx->last_ring_direct;
+    if (n > 12) c[12] = ctx->last_merge_variant;
     return HM_OK;
 }
 
@@ -395,6 +396,7 @@ int hm_process_batch(hm_ctx *ctx, int64_t epoch_id, const hm_batch_in *in, int32
     ctx->gmap_ready = true;
     ctx->dedup_seen = (int64_t)ctx->h_scratch[ctx->dlast->used_word];   // distinct vkeys of this batch
     DevStats s2 = *ctx->h_st;
+    if (s2.merge_hbm) ctx->last_merge_variant |= 8;
     if (s2.overflow) return set_err(ctx, HM_E_OVERFLOW, "device hash table overflow");
     if (s2.bad_vkey) return set_err(ctx, HM_E_INVALID, "vkey UINT64_MAX is reserved (%llu rows)", s2.bad_vkey);
     int64_t n_rows = (int64_t)ctx->h_scratch[255];

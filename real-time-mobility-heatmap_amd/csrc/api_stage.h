@@ -427,6 +427,7 @@ int hm_stage_merge(hm_ctx *ctx, const void *recv_buf, const int64_t *recv_bytes,
     HIPCHK(ctx, hipMemcpyAsync(ctx->h_st, ctx->d_st, sizeof(DevStats), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, ctx_sync(ctx, __LINE__));
     DevStats s2 = *ctx->h_st;
+    if (s2.merge_hbm) ctx->last_merge_variant |= 8;
     if (s2.overflow) return set_err(ctx, HM_E_OVERFLOW, "device hash table overflow");
     unsigned long long cur[64];
     unsigned long long acc = 0;

@@ -317,11 +317,13 @@ static int rows_densify(hm_ctx *ctx, int64_t ntiles, const unsigned long long *O
 
 // counters_zero: the merge's counters are still as k_batch_reset left them (the direct path, right after phase_local)
 static int merge_begin(hm_ctx *ctx, int64_t n_rows, bool counters_zero = false) {
-    static_assert(offsetof(DevStats, n_state_new) == offsetof(DevStats, n_touched) + 8, "DevStats");
+    static_assert(offsetof(DevStats, n_state_new) == offsetof(DevStats, n_touched) + 8 &&
+                  offsetof(DevStats, merge_hbm) == offsetof(DevStats, n_touched) + 16, "DevStats");
     if (!counters_zero) {
-        HIPCHK(ctx, hipMemsetAsync(&ctx->d_st->n_touched, 0, 16, ctx->stream));   // (+ n_state_new)
+        HIPCHK(ctx, hipMemsetAsync(&ctx->d_st->n_touched, 0, 24, ctx->stream));   // (+ n_state_new, merge_hbm)
         HIPCHK(ctx, hipMemsetAsync(&ctx->d_st->overflow, 0, 8, ctx->stream));
     }
+    ctx->last_merge_variant = 0;
     ctx->seq++;
     ctx->batch_windows.clear();
     return ensure_outputs(ctx, n_rows);

@@ -119,6 +119,11 @@ struct hm_ctx {
     int64_t prev_agg_rows = 0, prev_keys = 0;   // aggregated rows and distinct keys of the last batch
     bool merge_coop = false;   // the last batch's keys were mostly existing ones: the merge's cooperative probe
     bool coop_predict = true;  // MOBHEAT_COOP_PREDICT=0: the merge variant from the last batch (merge_coop) alone
+    int64_t test_merge_tags = -1;   // MOBHEAT_TEST_MERGE_TAGS: at most this many bytes of resident tags (tests; -1: unset)
+    int test_merge_coop = -1;       // MOBHEAT_TEST_MERGE_COOP=0|1: the probe of a resident merge (tests; -1: unset)
+    // hm_last_counts [12]: the variant of the batch's last k_merge_owned launch (merge_sorted; growth's not recorded) --
+    // 1 resident-only, 2 cooperative probe, 4 segments; 8 (DevStats.merge_hbm) is added when the batch's counters are read
+    int64_t last_merge_variant = 0;
     bool last_table = false;
     int64_t last_counts[6] = {0, 0, 0, 0, 0, 0};   // hm_last_counts [0, 6) ([6], [7]: n_allocs, n_frees)
     int64_t n_allocs = 0, n_frees = 0;             // device + pinned-host allocations / frees since create
@@ -711,6 +716,33 @@ struct Segs {
     int nseg = 0;
     SegBounds bounds{};   // where the segments may lie (checked by the MOBHEAT_BOUNDS_CHECK build only)
 };
+// The instantiations of k_merge_owned that are launched, listed once: the kernel for (Rec, resident, coop, segs), nullptr
+// where there is none.  merge_sorted launches what this returns and hm_create sets the dynamic-LDS attribute of
+// everything it returns (for_each_merge_variant), so a launched variant cannot miss its attribute.
+template <typename Rec>
+static auto merge_variant(bool resident, bool coop, bool segs) -> decltype(&k_merge_owned<Rec>) {
+    if (coop && !resident) return nullptr;   // (the cooperative probe needs every window resident)
+    if constexpr (std::is_same<Rec, GrowRec>::value) {   // growth probes the new tables through HBM
+        return resident || segs ? nullptr : k_merge_owned<Rec, false>;
+    } else if constexpr (std::is_same<Rec, EventRec>::value) {
+        if (segs) return !resident ? k_merge_owned<Rec, false, false, true> : coop ? k_merge_owned<Rec, true, true, true> : k_merge_owned<Rec, true, false, true>;
+        return !resident ? k_merge_owned<Rec, false> : coop ? k_merge_owned<Rec, true, true> : k_merge_owned<Rec, true>;
+    } else {
+        if (segs) return nullptr;   // (table mode's and the stage merge's partials are one array)
+        return !resident ? k_merge_owned<Rec, false> : coop ? k_merge_owned<Rec, true, true> : k_merge_owned<Rec, true>;
+    }
+}
+template <typename F>
+static bool for_each_merge_variant(F f) {   // f(kernel) -> bool; false stops
+    for (int v = 0; v < 8; v++) {
+        const bool r = v & 1, c = v & 2, s = v & 4;
+        const void *k[3] = {(const void *)merge_variant<EventRec>(r, c, s), (const void *)merge_variant<SortedRec>(r, c, s),
+                            (const void *)merge_variant<GrowRec>(r, c, s)};
+        for (const void *p : k)
+            if (p && !f(p)) return false;
+    }
+    return true;
+}
 // merge the partitioned records (ctx->parts_sorted, or src) of n_rows staging rows
 // (O / cnt: the bins' row offsets and their touched-key counts; default rp_O and bin_cnt -- a pipelined batch's chunk k
 // passes its own slices of pl_O / pl_cnt)
@@ -728,25 +760,25 @@ static int merge_sorted(hm_ctx *ctx, int64_t n_rows, int64_t ntiles, int64_t sla
             (rc = ensure(ctx, ctx->s_lat, m * 8)))
             return rc;
     }
-    // resident tags: every window merged into this batch may have a region in a bin
-    unsigned tag_bytes = 0;
-    if (!rehash) {
-        size_t need = 0;
+    // resident tags: every window merged into this batch may have a region in a bin (need: their tags together)
+    size_t need = 0;
+    int nwin = 0;
+    int64_t old = 0, parts = 0;   // the batch's records, and those of them whose window already holds that many keys
+    if (!rehash)
         for (const auto &g : ctx->gens)
-            if (g.batch_parts) need += size_t(1) << (g.log2cap - (int)g.rbits);
-        tag_bytes = (unsigned)std::min<size_t>((need + 4095) & ~size_t(4095), MO_TAG_MAX);   // (attribute: hm_create)
-    }
+            if (g.batch_parts) {
+                need += size_t(1) << (g.log2cap - (int)g.rbits);
+                nwin++;
+                parts += g.batch_parts;
+                old += std::min(g.keys, g.batch_parts);
+            }
+    size_t tags = std::min<size_t>((need + 4095) & ~size_t(4095), MO_TAG_MAX);   // (attribute: hm_create)
+    if (ctx->test_merge_tags >= 0) tags = std::min<size_t>(tags, (size_t)ctx->test_merge_tags);
+    const unsigned tag_bytes = (unsigned)tags;
     const int grid = ctx->merge_grid > 0 ? std::min(ctx->merge_grid, RP_BINS) : RP_BINS;
     // every window of the batch resident in every bin (their regions' tags fit together): the variant without the
     // HBM-probing fallback
-    bool resident = false;
-    if (!rehash) {
-        size_t need = 0;
-        int nwin = 0;
-        for (const auto &g : ctx->gens)
-            if (g.batch_parts) { need += size_t(1) << (g.log2cap - (int)g.rbits); nwin++; }
-        resident = need <= tag_bytes && nwin <= MO_RES_MAX && ctx->n_glist <= GC_MAX;
-    }
+    const bool resident = !rehash && need <= tag_bytes && nwin <= MO_RES_MAX && ctx->n_glist <= GC_MAX;
     if (seg.nseg > MO_SEG_MAX) return set_err(ctx, HM_E_INVALID, "%d senders exceed %d", seg.nseg, MO_SEG_MAX);
 #if MOBHEAT_BOUNDS_CHECK
     if (seg.nseg > 0) HIPCHK(ctx, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_seg_bounds), &seg.bounds, sizeof(SegBounds), 0,
@@ -755,37 +787,19 @@ static int merge_sorted(hm_ctx *ctx, int64_t n_rows, int64_t ntiles, int64_t sla
     // the cooperative probe (re-touched keys: old lines read) when this batch's windows already hold keys for most of
     // its records -- known here from the census and the tables, where the last batch's ratio (merge_coop) mispredicts
     // the batch after a window opened (all new keys, then all re-touched: 6.8-ms merges, profiles/r5/r5headprof)
-    bool coop = ctx->merge_coop;
-    if (!rehash && ctx->coop_predict) {
-        int64_t old = 0, parts = 0;
-        for (const auto &g : ctx->gens)
-            if (g.batch_parts) { parts += g.batch_parts; old += std::min(g.keys, g.batch_parts); }
-        coop = parts > 0 && 2 * old > parts;
-    }
-    auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(MO_THREADS), tag_bytes, ctx->stream, src ? src : (const Rec *)ctx->parts_sorted.p, slab,
-                           seg.SO, seg.SP, seg.nseg,
-                           O ? O : (const unsigned long long *)ctx->rp_O.p, ntiles, RP_BINS, ctx->d_gmap, (const GenDesc *)ctx->d_glist,
-                           ctx->n_glist, (const WInfo *)ctx->d_winfo, cell_hi_of(ctx->cfg.h3_res), seq32(ctx), staged_rows(ctx),
-                           cnt ? cnt : (unsigned *)ctx->bin_cnt.p, ctx->d_st, tag_bytes);
-    };
-    if constexpr (std::is_same<Rec, EventRec>::value) {
-        if (seg.nseg > 0) {   // (the multi-GPU owner)
-            if (resident && coop) launch(k_merge_owned<Rec, true, true, true>);
-            else if (resident) launch(k_merge_owned<Rec, true, false, true>);
-            else launch(k_merge_owned<Rec, false, false, true>);
-            HIPCHK(ctx, hipGetLastError());
-            return HM_OK;
-        }
-    }
-    if constexpr (!rehash) {
-        if (resident && coop) launch(k_merge_owned<Rec, true, true>);
-        else if (resident) launch(k_merge_owned<Rec, true>);
-        else launch(k_merge_owned<Rec, false>);
-    } else {
-        launch(k_merge_owned<Rec, false>);
-    }
+    bool coop = ctx->coop_predict ? parts > 0 && 2 * old > parts : ctx->merge_coop;
+    if (ctx->test_merge_coop >= 0) coop = ctx->test_merge_coop != 0;
+    coop = coop && resident;   // (the cooperative probe is the resident-only merge's)
+    const bool segs = seg.nseg > 0;   // (the multi-GPU owner, a binned batch's sub-slabs)
+    const auto kern = merge_variant<Rec>(resident, coop, segs);
+    if (!kern) return set_err(ctx, HM_E_STATE, "no merge variant for these records (resident %d, segments %d)", resident, segs);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(MO_THREADS), tag_bytes, ctx->stream, src ? src : (const Rec *)ctx->parts_sorted.p, slab,
+                       seg.SO, seg.SP, seg.nseg,
+                       O ? O : (const unsigned long long *)ctx->rp_O.p, ntiles, RP_BINS, ctx->d_gmap, (const GenDesc *)ctx->d_glist,
+                       ctx->n_glist, (const WInfo *)ctx->d_winfo, cell_hi_of(ctx->cfg.h3_res), seq32(ctx), staged_rows(ctx),
+                       cnt ? cnt : (unsigned *)ctx->bin_cnt.p, ctx->d_st, tag_bytes);
     HIPCHK(ctx, hipGetLastError());
+    if (!rehash) ctx->last_merge_variant = (resident ? 1 : 0) | (coop ? 2 : 0) | (segs ? 4 : 0);
     return HM_OK;
 }
 

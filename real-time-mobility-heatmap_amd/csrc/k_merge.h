@@ -57,12 +57,12 @@ __global__ __launch_bounds__(256) void k_dump_gen(GenDesc g, GrowRec *__restrict
 
 // =====================================================================================================
 // K3': owner merge + emission. The workgroup of a bin is the only writer of the (window, region)s the partition
-// sent it, so the state is updated with plain loads/stores instead of device-scope atomics. Per chunk of 256
-// partials (one per lane), each lane finds its key's slot and claims it in an LDS claim set keyed by slot
-// address; a lane whose slot is already claimed by the same key in this chunk adds its values into the
-// claimer's LDS staging entry and is done (in-chunk de-duplication without a separate hash table):
+// sent it, so the state is updated with plain loads/stores instead of device-scope atomics. Per chunk of 512
+// partials (one per lane), each lane finds its key's slot and claims it in an LDS claim set (MoClaims); a lane whose
+// slot is already claimed by the same key in this chunk adds its values into the claimer's LDS staging entry and is
+// done (in-chunk de-duplication without a separate hash table):
 //  * resident windows (the bin's regions of the windows this batch merges into, while their tags fit in
-//    MO_TAG_BYTES of LDS): probing runs over the region's slot tags in LDS -- a new key reads nothing from HBM;
+//    tag_bytes of LDS): probing runs over the region's slot tags in LDS -- a new key reads nothing from HBM;
 //    an occupied slot not claimed in this chunk is read only on a tag match;
 //  * other windows (too many/too large regions, or growth): probing reads the slots' window words from HBM;
 //    the tag byte of a created slot is stored to HBM.
@@ -73,12 +73,16 @@ __global__ __launch_bounds__(256) void k_dump_gen(GenDesc g, GrowRec *__restrict
 // that had several partials.
 // rehash != 0: growth (k_dump_gen records, unique keys, into the window's new table): created slots keep the
 // record's touched word, no rows are written.
+// The kernel is its bin loop and chunk loop over these steps, each a function below:
+//   per bin    0  mo_resident_regions (+ mo_load_segments), mo_fill_tags
+//   per chunk  1  mo_rec_at, mrec_of, mo_stage          2  mo_probe / mo_probe_coop     3a mo_old_line
+//              3  mo_touch_rows, mo_new_line            4  mo_store_lines, put_row      5  barrier, MoClaims::release
+//   per bin    6  mo_tags_writeback
 // =====================================================================================================
 constexpr int MO_THREADS = 512;      // partials per chunk (one per lane)
-// the resident-only merge's wave-cooperative probe (needs the early-lines scratch)
-// claim-set entries per record of a chunk (the resident-only merge: 2x as many 32-bit entries; 2 + the early old-line
-// scratch fit the same LDS as 4 without it)
-constexpr int MO_CLAIM = 2 * MO_THREADS;   // claim-set entries (load <= 1/2)
+// The LDS of a chunk's claim set holds MO_CLAIM 64-bit entries keyed by slot address (load <= 1/2) or, in the
+// resident-only merge, MO_CLAIM32 32-bit entries keyed by tag index (load <= 1/4): MoClaims below.
+constexpr int MO_CLAIM = 2 * MO_THREADS;
 // LDS for resident region tags per workgroup: dynamic, sized per launch to the regions a bin can receive (the sum
 // over the batch's windows of slots per region, 1 B each) up to MO_TAG_MAX -- 24 KB on the bench (3 windows x 8 K
 // slots: two workgroups per CU), 32 KB for a res-7 window of 2^28 slots, which would otherwise probe through HBM
@@ -94,7 +98,7 @@ struct MoShared {
     double sssp[MO_THREADS];
     double sslat[MO_THREADS];
     double sslon[MO_THREADS];
-    unsigned long long claim[MO_CLAIM];   // (slot address << 16) | claimer lane; 0 = free
+    unsigned long long claim[MO_CLAIM];   // the claim set (MoClaims); 0 = free
     unsigned n_touched;                   // keys of the current bin touched for the first time this batch
     int n_res;
     unsigned res_new[MO_RES_MAX];         // keys created in the resident region this bin
@@ -113,58 +117,51 @@ __device__ __forceinline__ T ld_l2(const T *p) {   // bypass the CU's L1 (chunks
     // flat instruction, which also counts on lgkmcnt -- so each later LDS wait waited for it to complete)
     return __hip_atomic_load((__attribute__((address_space(1))) const T *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ unsigned mo_claim_home(unsigned long long addr) {
-    return (unsigned)(((addr >> 6) * UINT64_C(0x9e3779b97f4a7c15)) >> 40) & (MO_CLAIM - 1);
-}
-// claim slot `addr` for `lane` in claim set cl: -1 = claimed (entry index in ci), else the lane that already holds it
-__device__ __forceinline__ int mo_claim(unsigned long long *cl, unsigned long long addr, int lane, int &ci) {
-    const unsigned long long packed = (addr << 16) | (unsigned)lane;
-    unsigned h = mo_claim_home(addr);
-    for (int k = 0; k < MO_CLAIM; k++) {
-        const unsigned long long o = atomicCAS(&cl[h], 0ull, packed);
-        if (o == 0) { ci = (int)h; return -1; }
-        if ((o >> 16) == addr) return (int)(o & 0xffff);
-        h = (h + 1) & (MO_CLAIM - 1);
+
+// The claim set of a chunk in S.claim: open addressing, an entry is ((key + kBias) << kLaneBits) | claimer lane, 0 = free.
+//  * MoClaimsAddr: 64-bit entries keyed by the slot's address (the variants that may probe through HBM);
+//  * MoClaimsTag: the resident-only merge keys its claims by the slot's tag index (< 2^17: MO_TAG_MAX) instead, so an
+//    entry is 32 bits -- ((tag index + 1) << 9) | lane -- and the same LDS holds twice the entries.
+template <typename E, int kLaneBits, int kEntries>
+struct MoClaims {
+    typedef E Key;
+    static constexpr E kBias = sizeof(E) == 4 ? 1 : 0;   // (a tag index may be 0; an address is not)
+    E *cl;
+    static __device__ __forceinline__ unsigned home(E key) {
+        if constexpr (sizeof(E) == 8) return (unsigned)(((key >> 6) * UINT64_C(0x9e3779b97f4a7c15)) >> 40) & (kEntries - 1);
+        else return (key * 0x9e3779b1u) >> (32 - __builtin_ctz(kEntries));
     }
-    return -2;
-}
-// the lane holding slot `addr` in claim set cl, -1 if none
-__device__ __forceinline__ int mo_holder(const unsigned long long *cl, unsigned long long addr) {
-    unsigned h = mo_claim_home(addr);
-    for (int k = 0; k < MO_CLAIM; k++) {
-        const unsigned long long o = __hip_atomic_load(&cl[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (o == 0) return -1;
-        if ((o >> 16) == addr) return (int)(o & 0xffff);
-        h = (h + 1) & (MO_CLAIM - 1);
+    // claim `key` for `lane`: -1 = claimed (entry index in ci), else the lane that already holds it (-2: the set is full)
+    __device__ __forceinline__ int claim(E key, int lane, int &ci) const {
+        const E packed = ((key + kBias) << kLaneBits) | (E)lane;
+        unsigned h = home(key);
+        for (int k = 0; k < kEntries; k++) {
+            const E o = atomicCAS(&cl[h], (E)0, packed);
+            if (o == 0) { ci = (int)h; return -1; }
+            if ((o >> kLaneBits) == key + kBias) return (int)(o & ((E(1) << kLaneBits) - 1));
+            h = (h + 1) & (kEntries - 1);
+        }
+        return -2;
     }
-    return -1;
-}
-// The resident-only merge keys its claims by the slot's tag index (< 2^17: MO_TAG_MAX) instead of its address, so an
-// entry is 32 bits -- ((tag index + 1) << 9) | claimer lane -- and the same LDS holds twice the entries (load <= 1/8).
+    // the lane holding `key`, -1 if none
+    __device__ __forceinline__ int holder(E key) const {
+        unsigned h = home(key);
+        for (int k = 0; k < kEntries; k++) {
+            const E o = __hip_atomic_load(&cl[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (o == 0) return -1;
+            if ((o >> kLaneBits) == key + kBias) return (int)(o & ((E(1) << kLaneBits) - 1));
+            h = (h + 1) & (kEntries - 1);
+        }
+        return -1;
+    }
+    __device__ __forceinline__ void release(int ci) const { cl[ci] = 0; }
+};
 constexpr int MO_CLAIM32 = 2 * MO_CLAIM;
 static_assert(MO_TAG_MAX < (1 << 17) && MO_THREADS <= 512, "32-bit claim entries");
-__device__ __forceinline__ unsigned mo_claim_home32(unsigned key) { return (key * 0x9e3779b1u) >> (32 - __builtin_ctz(MO_CLAIM32)); }
-__device__ __forceinline__ int mo_claim32(unsigned *cl, unsigned key, int lane, int &ci) {
-    const unsigned packed = ((key + 1) << 9) | (unsigned)lane;
-    unsigned h = mo_claim_home32(key);
-    for (int k = 0; k < MO_CLAIM32; k++) {
-        const unsigned o = atomicCAS(&cl[h], 0u, packed);
-        if (o == 0) { ci = (int)h; return -1; }
-        if ((o >> 9) == key + 1) return (int)(o & 511u);
-        h = (h + 1) & (MO_CLAIM32 - 1);
-    }
-    return -2;
-}
-__device__ __forceinline__ int mo_holder32(const unsigned *cl, unsigned key) {
-    unsigned h = mo_claim_home32(key);
-    for (int k = 0; k < MO_CLAIM32; k++) {
-        const unsigned o = __hip_atomic_load(&cl[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (o == 0) return -1;
-        if ((o >> 9) == key + 1) return (int)(o & 511u);
-        h = (h + 1) & (MO_CLAIM32 - 1);
-    }
-    return -1;
-}
+typedef MoClaims<unsigned long long, 16, MO_CLAIM> MoClaimsAddr;
+typedef MoClaims<unsigned, 9, MO_CLAIM32> MoClaimsTag;
+template <bool kResident> using MoClaimsOf = typename std::conditional<kResident, MoClaimsTag, MoClaimsAddr>::type;
+
 // a merge input record, normalised: SortedRec (table mode / stage merge), GrowRec (growth), EventRec (direct path)
 struct MRec {
     uint64_t cell;
@@ -186,10 +183,7 @@ __device__ __forceinline__ MRec mrec_of_wi(const EventRec &p, const WInfo &wi, u
     return MRec{cell, wi.wenc, mix64(cell ^ wi.inner), 1ull, sv ? 1ull : 0ull, sv ? p.speed : 0.0, p.lat, p.lon, 0ull};
 }
 __device__ __forceinline__ MRec mrec_of(const EventRec &p, const WInfo *winfo, uint64_t cell_hi) {
-    const WInfo &wi = winfo[ekey_widx(p.key)];   // (an LDS copy measured no faster here: the chunk loop hides it)
-    const uint64_t cell = (p.key & CELL_LO) | cell_hi;
-    const bool sv = __builtin_bit_cast(uint64_t, p.speed) != SPEED_NULL_BITS;
-    return MRec{cell, wi.wenc, mix64(cell ^ wi.inner), 1ull, sv ? 1ull : 0ull, sv ? p.speed : 0.0, p.lat, p.lon, 0ull};
+    return mrec_of_wi(p, winfo[ekey_widx(p.key)], cell_hi);   // (an LDS copy measured no faster here: the chunk loop hides it)
 }
 // a duplicate of lane x's key: add this record's values into x's staging entry
 __device__ __forceinline__ void mo_add_into(MoShared &S, int x, const MRec &p) {
@@ -232,22 +226,119 @@ __device__ __forceinline__ void put_row(const RowsOut &o, int64_t t, uint64_t ce
     o.lat[t] = alat;
 }
 
-// a state line's new values (cell and window word are the key's)
+// a state line's values (cell and window word are the key's), and the line as its four 16-B parts (TileSlot's layout:
+// cell, wenc | count, nspeed | sspeed, slat | slon, touched)
 struct MLine {
     unsigned long long count, nspeed;
     double sspeed, slat, slon;
     unsigned long long touched;
 };
+struct MoLineParts { uint4 q0, q1, q2, q3; };
+__device__ __forceinline__ unsigned long long mo_u64(unsigned lo, unsigned hi) { return (unsigned long long)lo | ((unsigned long long)hi << 32); }
+__device__ __forceinline__ uint4 mo_u4(unsigned long long a, unsigned long long b) { return make_uint4((unsigned)a, (unsigned)(a >> 32), (unsigned)b, (unsigned)(b >> 32)); }
+__device__ __forceinline__ MLine mo_unpack_line(const MoLineParts &L) {
+    return MLine{mo_u64(L.q1.x, L.q1.y), mo_u64(L.q1.z, L.q1.w), __builtin_bit_cast(double, mo_u64(L.q2.x, L.q2.y)),
+                 __builtin_bit_cast(double, mo_u64(L.q2.z, L.q2.w)), __builtin_bit_cast(double, mo_u64(L.q3.x, L.q3.y)),
+                 mo_u64(L.q3.z, L.q3.w)};
+}
+__device__ __forceinline__ MoLineParts mo_pack_line(uint64_t cell, unsigned long long we, const MLine &v) {
+    return MoLineParts{mo_u4(cell, we), mo_u4(v.count, v.nspeed),
+                       mo_u4(__builtin_bit_cast(uint64_t, v.sspeed), __builtin_bit_cast(uint64_t, v.slat)),
+                       mo_u4(__builtin_bit_cast(uint64_t, v.slon), v.touched)};
+}
+// Whole lines per memory instruction, through LDS scratch of the wave (xa, xb: 32 16-B words each).  Every lane of the
+// wave calls these (shuffles); ga = the lane's slot address, 0 for none.  In round k, lanes 16k..16k+15 own the lines
+// and lane L moves part L & 3 of the line of lane 16k + L / 4: each 16-B instruction touches 16 whole 64-B lines
+// instead of a quarter of 64.
+// mo_gather_lines: the lanes' lines, loaded (16-B non-temporal loads: L2-served, like ld_l2); a round none of whose
+// 16 lanes has a line is skipped (wave-uniform).
+__device__ __forceinline__ MoLineParts mo_gather_lines(unsigned long long ga, uint4 *xa, uint4 *xb) {
+    MoLineParts L{};
+    const int ln = lane_id();
+    const unsigned long long needm = __ballot(ga != 0);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (!((needm >> (16 * k)) & 0xffffull)) continue;   // (wave-uniform)
+        const int src = k * 16 + (ln >> 2), part = ln & 3;
+        const unsigned long long sa = __shfl(ga, src, 64);
+        if (sa) {
+            const hm_v4u v = __builtin_nontemporal_load((g_cv4u *)sa + part);
+            ((part < 2) ? xa : xb)[(src & 15) * 2 + (part & 1)] = make_uint4(v.x, v.y, v.z, v.w);
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        if (ga && (ln >> 4) == k) {
+            const int e = (ln & 15) * 2;
+            L = MoLineParts{xa[e], xa[e + 1], xb[e], xb[e + 1]};
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    }
+    return L;
+}
+// mo_scatter_lines: the lanes' lines L, stored (the mirror of the gather; each lane storing its own line would be four
+// instructions, each touching 64 different lines)
+__device__ __forceinline__ void mo_scatter_lines(unsigned long long ga, const MoLineParts &L, uint4 *xa, uint4 *xb) {
+    const int ln = lane_id();
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if ((ln >> 4) == k) {
+            const int e = (ln & 15) * 2;
+            xa[e] = L.q0; xa[e + 1] = L.q1;
+            xb[e] = L.q2; xb[e + 1] = L.q3;
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        const int src = k * 16 + (ln >> 2), part = ln & 3;
+        const unsigned long long sa = __shfl(ga, src, 64);
+        const uint4 val = ((part < 2) ? xa : xb)[(src & 15) * 2 + (part & 1)];
+        if (sa) st_g16((uint4 *)sa + part, val);
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    }
+}
+
+// Advance (s, scanned) over the tags of a resident region (tag bytes [off, off + rmask] of `tags`, in LDS) to the next
+// slot whose tag is empty or tg: true with that slot in s and its tag in b, false when the region has none left.
+// Tags are scanned 8 at a time (one 8-B LDS read): only slots whose tag is empty or this key's are visited one by one,
+// so a wave's loop runs its lanes' longest count of such slots, not of probed slots.
+// (regions are >= 256 slots and start at multiples of their size: a word never crosses a region)
+__device__ __forceinline__ bool mo_tag_scan(const unsigned *tags, unsigned off, unsigned rmask, unsigned tg, unsigned &s,
+                                            unsigned &scanned, unsigned &b) {
+    const unsigned long long tgv = (unsigned long long)tg * UINT64_C(0x0101010101010101);
+    const unsigned long long *tags64 = (const unsigned long long *)tags;
+    while (scanned <= rmask) {
+        const unsigned bw = off + s, p0 = bw & 7;
+        const unsigned long long word = __hip_atomic_load(&tags64[bw >> 3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        // high bit of each byte that is 0 (exact per byte: no borrow between bytes), or equal to tg
+        constexpr unsigned long long LO7 = UINT64_C(0x7f7f7f7f7f7f7f7f);
+        const unsigned long long y = word ^ tgv;
+        unsigned long long cand = ~(((word & LO7) + LO7) | word | LO7) | ~(((y & LO7) + LO7) | y | LO7);
+        cand &= ~UINT64_C(0) << (8 * p0);
+        if (!cand) {   // no candidate in the rest of the word: the next word
+            scanned += 8 - p0;
+            s = (s + 8 - p0) & rmask;
+            continue;
+        }
+        const unsigned pos = (unsigned)__builtin_ctzll(cand) >> 3;
+        scanned += pos - p0 + 1;
+        s = (s + pos - p0) & rmask;
+        b = (unsigned)(word >> (8 * pos)) & 0xffu;
+        return true;
+    }
+    return false;
+}
 
 // Rec = SortedRec: a batch's partials (partitioned); EventRec: the direct path's rows; GrowRec: growth (rehash).
 // kResident: the host found every window of the batch resident in every bin (merge_sorted), so the variant carries
 // no HBM-probing fallback (less code, fewer live registers); a record outside the resident windows sets overflow.
-// kCoop (resident only): the wave-cooperative probe (probe_coop) -- chosen when the last batch re-touched mostly
+// kCoop (resident only): the wave-cooperative probe (mo_probe_coop) -- chosen when the last batch re-touched mostly
 // existing keys (their lines then cost one cooperative round trip); a batch of mostly new keys runs the per-lane probe,
 // which carries less machinery per probed slot (bench leg: 3.72-3.81 vs 4.03-4.11 ms; state-read leg: 6.86-6.89 vs
 // 6.22-6.30 ms, profiles/r3/r3ab9/)
 // kSeg (the multi-GPU owner): bin b's records are nseg segments, one per sender -- segment s at address SO[b * nseg + s]
 // (the receive buffer, or the owner's own slab), after SP[b * nseg + s] records of the bin (k_stage_segments)
+// The instantiations that are launched are listed once, in merge_variant (host_ctx.h).
 constexpr int MO_SEG_MAX = 64;
 // Debug build (make libmobheat_dbg.so: MOBHEAT_BOUNDS_CHECK=1): every segment read of the kSeg variant must lie in one
 // of the two ranges the host declared for the launch (merge_sorted: the receive buffer, the owner's slabs) -- else the
@@ -255,12 +346,308 @@ constexpr int MO_SEG_MAX = 64;
 #ifndef MOBHEAT_BOUNDS_CHECK
 #define MOBHEAT_BOUNDS_CHECK 0
 #endif
-struct SegBounds {
-    unsigned long long lo[2], hi[2];
-};
+struct SegBounds { unsigned long long lo[2], hi[2]; };
 #if MOBHEAT_BOUNDS_CHECK
 __device__ SegBounds g_seg_bounds;
 #endif
+
+// what the steps of one bin share (wave-uniform): the workgroup's LDS, the bin's records [b0, b1) and resident regions,
+// the kSeg variant's segment tables (in LDS)
+struct MoBin {
+    MoShared &S;
+    unsigned *tags;   // the resident regions' tags (dynamic LDS)
+    int bin;
+    int64_t b0, b1;
+    int nres;
+    const unsigned long long *seg_base;   // kSeg: segment s's first record, after seg_pre[s] records of the bin
+    const unsigned *seg_pre;
+    int nseg;
+};
+
+// 0. the bin's resident regions: windows merged into this batch whose region maps to this bin (one thread)
+__device__ __forceinline__ void mo_resident_regions(MoShared &S, const GenCache &C, int bin, bool any, unsigned tag_bytes) {
+    int nr = 0;
+    unsigned off = 0;
+    if (any && C.n >= 0) {
+        for (int q = 0; q < C.n; q++) {
+            const GenDesc &g = C.e[q];
+            if (!g.batch_parts) continue;
+            const unsigned sb = g.sb, smask = (1u << sb) - 1;
+            if (((unsigned)bin & smask) != (window_salt(g.wenc) & smask)) continue;
+            const unsigned reg = ((unsigned)bin >> sb) - g.rbase;   // (a shard's table: its range only)
+            if (reg >= (1u << g.rbits)) continue;
+            const unsigned slots = (unsigned)g.rmask + 1;
+            if (nr == MO_RES_MAX || off + slots > tag_bytes) continue;
+            const unsigned long long first = (unsigned long long)reg << g.rshift;
+            S.res_we[nr] = g.wenc;
+            S.res_slots[nr] = g.tab + first;
+            S.res_gtags[nr] = gen_tags(g) + first;
+            S.res_off[nr] = off;
+            S.res_mask[nr] = slots - 1;
+            S.res_dirty[nr] = 0;
+            S.res_new[nr] = 0;
+            off += slots;
+            nr++;
+        }
+    }
+    S.n_res = nr;
+}
+// the resident regions' tags into LDS (16-B words, regions >= 256 slots): every load of a thread in flight together
+__device__ __forceinline__ void mo_fetch_tag_word(const MoShared &S, unsigned q, unsigned tot, uint4 &v, unsigned &a) {
+    typedef __attribute__((address_space(1))) const hm_v4u gv4u;   // global loads (the pointers sit in LDS)
+    if (q >= tot) return;
+    unsigned w = q;
+    int r = 0;
+    while (w >= ((S.res_mask[r] + 1) >> 4)) { w -= (S.res_mask[r] + 1) >> 4; r++; }
+    const hm_v4u x = ((gv4u *)S.res_gtags[r])[w];
+    v = make_uint4(x.x, x.y, x.z, x.w);
+    a = (S.res_off[r] >> 4) + w;
+}
+__device__ __forceinline__ void mo_fill_tags(const MoBin &B, int t) {
+    const MoShared &S = B.S;
+    unsigned tot = 0;
+    for (int r = 0; r < B.nres; r++) tot += (S.res_mask[r] + 1) >> 4;
+    for (unsigned q0 = t; q0 < tot; q0 += 4 * MO_THREADS) {
+        uint4 v0, v1, v2, v3;
+        unsigned a0 = ~0u, a1 = ~0u, a2 = ~0u, a3 = ~0u;
+        mo_fetch_tag_word(S, q0, tot, v0, a0);
+        mo_fetch_tag_word(S, q0 + MO_THREADS, tot, v1, a1);
+        mo_fetch_tag_word(S, q0 + 2 * MO_THREADS, tot, v2, a2);
+        mo_fetch_tag_word(S, q0 + 3 * MO_THREADS, tot, v3, a3);
+        if (a0 != ~0u) ((uint4 *)B.tags)[a0] = v0;
+        if (a1 != ~0u) ((uint4 *)B.tags)[a1] = v1;
+        if (a2 != ~0u) ((uint4 *)B.tags)[a2] = v2;
+        if (a3 != ~0u) ((uint4 *)B.tags)[a3] = v3;
+    }
+}
+
+// 1. record i of the bin: [b0, b1) of the partitioned array or of the bin's slab (bp), or (kSeg) the record at bin
+// index v = i - b0, in the last segment starting at or before v (binary search)
+template <typename Rec, bool kSeg>
+__device__ __forceinline__ const Rec *mo_rec_at(const MoBin &B, const Rec *__restrict__ bp, int64_t i) {
+    if constexpr (kSeg) {
+        const unsigned v = (unsigned)(i - B.b0);
+        int lo = 0, hi = B.nseg;   // seg_pre[lo] <= v < seg_pre[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (B.seg_pre[mid] <= v) lo = mid; else hi = mid;
+        }
+        const Rec *rp = (const Rec *)(uintptr_t)B.seg_base[lo] + (v - B.seg_pre[lo]);
+#if MOBHEAT_BOUNDS_CHECK
+        const unsigned long long a = (unsigned long long)(uintptr_t)rp, e = a + sizeof(Rec);
+        const SegBounds &G = g_seg_bounds;
+        if (!((a >= G.lo[0] && e <= G.hi[0]) || (a >= G.lo[1] && e <= G.hi[1]))) {
+            printf("k_merge_owned: bin %d segment %d record %u at 0x%llx outside [0x%llx, 0x%llx) and [0x%llx, 0x%llx)\n",
+                   B.bin, lo, v, a, G.lo[0], G.hi[0], G.lo[1], G.hi[1]);
+            __builtin_trap();
+        }
+#endif
+        return rp;
+    } else {
+        return bp + i;
+    }
+}
+// 1. lane t's record of this chunk, staged in LDS
+__device__ __forceinline__ void mo_stage(MoShared &S, int t, const MRec &p) {
+    S.sc[t] = p.cell; S.sh[t] = p.hk;
+    S.scnt[t] = p.cnt; S.snsp[t] = p.nsp; S.sssp[t] = p.ssp;
+    S.sslat[t] = p.slat; S.sslon[t] = p.slon;
+}
+
+// 2. what a lane's probe found
+struct MoProbe {
+    TileSlot *gslot = nullptr;   // the slot this lane claimed (nullptr: it joined the lane holding its key, or has no record)
+    bool created = false;        // the slot was empty
+    int r = -1, ci = -1;         // the key's resident region (-1: none), the lane's claim-set entry
+    MLine pre{}; bool preloaded = false;   // mo_probe_coop: the existing line, already loaded
+    bool lost = false;           // no slot found (a full region, a window without a table): overflow
+    bool hbm = false;            // probed through HBM
+};
+__device__ __forceinline__ int mo_region_of(const MoBin &B, unsigned long long we) {
+    int r = -1;
+    for (int q = 0; q < B.nres; q++) r = B.S.res_we[q] == we ? q : r;
+    return r;
+}
+// a claimed resident slot that was empty gets the key's tag
+__device__ __forceinline__ void mo_tag_created(const MoBin &B, int r, unsigned bi, unsigned tg) {
+    atomicOr(&B.tags[bi >> 2], tg << ((bi & 3) * 8));
+    B.S.res_dirty[r] = 1;
+}
+// find (and claim) the slot of lane t's key p, or join the lane of this chunk that holds it
+template <bool kResident>
+__device__ __forceinline__ void mo_probe(const MoBin &B, const GenCache &C, GenDesc *gm, const MRec &p, int t, MoProbe &o) {
+    typedef MoClaimsOf<kResident> Claims;
+    MoShared &S = B.S;
+    const Claims cl{(typename Claims::Key *)S.claim};
+    const unsigned long long we = p.we;
+    const uint64_t hk = p.hk;
+    const unsigned tg = tag8(hk);
+    bool done = false;
+    const int r = o.r = mo_region_of(B, we);
+    if (r >= 0) {
+        const unsigned rmask = S.res_mask[r], off = S.res_off[r];
+        TileSlot *const base = S.res_slots[r];
+        unsigned s = (unsigned)inreg_slot(hk, rmask), scanned = 0, b = 0;
+        while (!done && mo_tag_scan(B.tags, off, rmask, tg, s, scanned, b)) {
+            TileSlot *const sl = base + s;
+            const unsigned bi = off + s;
+            const typename Claims::Key key = kResident ? (typename Claims::Key)bi : (typename Claims::Key)(unsigned long long)sl;
+            int x = b == 0 ? -1 : cl.holder(key);
+            bool old_match = false;
+            if (b == tg && x < 0) old_match = ld_l2(&sl->cell) == p.cell && ld_l2(&sl->wenc) == we;
+            if (b == 0 || old_match) {
+                x = cl.claim(key, t, o.ci);
+                if (x == -1) {
+                    o.gslot = sl;
+                    o.created = b == 0;
+                    if (o.created) mo_tag_created(B, r, bi, tg);
+                    done = true;
+                }
+            }
+            if (!done && x >= 0 && S.sc[x] == p.cell && S.sh[x] == hk) {   // same key, this chunk
+                mo_add_into(S, x, p);
+                done = true;
+            }
+            s = (s + 1) & rmask;
+        }
+    } else if constexpr (!kResident) {
+        o.hbm = true;
+        const GenDesc *g = gen_lookup(C, gm, we);
+        if (g) {
+            TileSlot *const tab = g->tab;
+            const unsigned long long rmask = g->rmask;
+            unsigned long long sidx = home_slot(*g, hk);
+            for (unsigned long long pr = 0; pr <= rmask && !done; pr++) {
+                TileSlot *const sl = &tab[sidx];
+                const bool free_here = ld_l2(&sl->wenc) != we;   // never used, or another window's key
+                if (free_here || ld_l2(&sl->cell) == p.cell) {
+                    const int x = cl.claim((unsigned long long)sl, t, o.ci);
+                    if (x == -1) {
+                        o.gslot = sl;
+                        o.created = free_here;
+                        if (o.created) ((__attribute__((address_space(1))) uint8_t *)gen_tags(*g))[sidx] = (uint8_t)tag8(hk);
+                        done = true;
+                    } else if (S.sc[x] == p.cell && S.sh[x] == hk) {
+                        mo_add_into(S, x, p);
+                        done = true;
+                    }
+                }
+                sidx = next_slot(sidx, rmask);
+            }
+        }
+    }
+    if (!done) o.lost = true;
+}
+// The resident-only merge's probe, wave-cooperative: each round every lane still probing scans its region's
+// tags to its next candidate slot (empty or its tag); the lanes whose candidate holds an older key of the same
+// tag then load those lines TOGETHER, whole (mo_gather_lines), compare the key and keep the line: one round trip per
+// existing key, and no second load of the line after the barrier.  Every lane of the wave calls it (has: with a record).
+__device__ __forceinline__ void mo_probe_coop(const MoBin &B, const MRec &p, bool has, int t, MoProbe &o) {
+    MoShared &S = B.S;
+    const MoClaimsTag cl{(unsigned *)S.claim};
+    const unsigned long long we = p.we;
+    const uint64_t hk = p.hk;
+    const unsigned tg = tag8(hk);
+    const int r = o.r = has ? mo_region_of(B, we) : -1;
+    bool done = !has || r < 0;
+    o.lost = has && r < 0;
+    unsigned rmask = 0, off = 0, s = 0, scanned = 0;
+    TileSlot *base = nullptr;
+    if (r >= 0) {
+        rmask = S.res_mask[r];
+        off = S.res_off[r];
+        base = S.res_slots[r];
+        s = (unsigned)inreg_slot(hk, rmask);
+    }
+    uint4 *const xa = &S.xline[t >> 6][0], *const xb = &S.xline[t >> 6][32];
+    while (__ballot(!done)) {
+        // 1. this lane's next candidate slot
+        unsigned b = 0;
+        bool found = false;
+        if (!done) {
+            found = mo_tag_scan(B.tags, off, rmask, tg, s, scanned, b);
+            if (!found) { done = true; o.lost = true; }   // the region is full
+        }
+        const unsigned bi = off + s;
+        TileSlot *const sl = base + s;
+        // 2. a tag-matching slot: claimed in this chunk (its holder), else its line from HBM, loaded together
+        int x = -1;
+        if (found && b != 0) x = cl.holder(bi);
+        const bool need = found && b == tg && x < 0;
+        const MoLineParts L = mo_gather_lines(need ? (unsigned long long)sl : 0ull, xa, xb);
+        const bool old_match = need && mo_u64(L.q0.x, L.q0.y) == p.cell && mo_u64(L.q0.z, L.q0.w) == we;
+        // 3. claim an empty slot or the key's own
+        if (found && (b == 0 || old_match)) {
+            x = cl.claim(bi, t, o.ci);
+            if (x == -1) {
+                o.gslot = sl;
+                o.created = b == 0;
+                if (o.created) mo_tag_created(B, r, bi, tg);
+                else { o.pre = mo_unpack_line(L); o.preloaded = true; }
+                done = true;
+            }
+        }
+        if (found && !done && x >= 0 && S.sc[x] == p.cell && S.sh[x] == hk) {   // same key, this chunk
+            mo_add_into(S, x, p);
+            done = true;
+        }
+        if (found && !done) s = (s + 1) & rmask;
+    }
+}
+
+// 3a. the claimed slot's current line (created slots read nothing; mo_probe_coop's lanes have theirs): whole lines per
+// load instruction through the wave's own scratch -- the lines are loaded before the barrier, while other waves'
+// joiners still read this wave's staged keys in S.sc / S.sh.  Every lane of the wave calls it.
+__device__ __forceinline__ MLine mo_old_line(MoShared &S, int t, const MoProbe &pr) {
+    MLine o{};
+    if (pr.preloaded) o = pr.pre;
+    const bool need = pr.gslot && !pr.created && !pr.preloaded;
+    const MoLineParts L = mo_gather_lines(need ? (unsigned long long)pr.gslot : 0ull, &S.xline[t >> 6][0], &S.xline[t >> 6][32]);
+    if (need) o = mo_unpack_line(L);
+    return o;
+}
+// 3. row index of a key's first touch in this batch: one LDS add per wave
+__device__ __forceinline__ unsigned mo_touch_rows(MoShared &S, bool first) {
+    const unsigned long long fb = __ballot(first);
+    unsigned tbase = 0;
+    if (lane_id() == 0 && fb) tbase = atomicAdd(&S.n_touched, (unsigned)__popcll(fb));
+    tbase = __shfl(tbase, 0, 64);
+    return tbase + (unsigned)__popcll(fb & ((1ull << lane_id()) - 1));
+}
+// 3. the new state line of a claimed slot: its old values (o) + the chunk's sums for the key in lane t's staging entry
+template <bool rehash>
+__device__ __forceinline__ MLine mo_new_line(const MoShared &S, int t, const MRec &p, const MLine &o, bool first, unsigned seq,
+                                             unsigned krow) {
+    MLine v;
+    const unsigned long long acnt = S.scnt[t], ansp = S.snsp[t];
+    v.count = o.count + acnt;
+    v.nspeed = o.nspeed + ansp;
+    v.sspeed = ansp ? o.sspeed + S.sssp[t] : o.sspeed;
+    v.slat = o.slat + S.sslat[t];
+    v.slon = o.slon + S.sslon[t];
+    if constexpr (rehash) v.touched = p.touched;
+    else v.touched = first ? ((unsigned long long)seq << 32) | krow : o.touched;
+    return v;
+}
+// 4. this chunk's state lines, stored whole: the lanes' lines go through the wave's slices of S.sc / S.sh, unused
+// after the probe.  Every lane of the wave calls it (gslot == nullptr: nothing to store).
+__device__ __forceinline__ void mo_store_lines(MoShared &S, int t, TileSlot *gslot, const MRec &p, const MLine &v) {
+    mo_scatter_lines((unsigned long long)gslot, mo_pack_line(p.cell, p.we, v), (uint4 *)&S.sc[t & ~63], (uint4 *)&S.sh[t & ~63]);
+}
+// 6. the bin's created keys counted for their windows, and the resident regions' tags written back
+__device__ __forceinline__ bool mo_tags_writeback(const MoBin &B, GenDesc *gm, int t) {
+    const MoShared &S = B.S;
+    bool ok = true;
+    if (t < B.nres && S.res_new[t] && !gmap_add(gm, S.res_we[t], S.res_new[t])) ok = false;
+    for (int r = 0; r < B.nres; r++) {
+        if (!S.res_dirty[r]) continue;
+        uint4 *dst = (uint4 *)S.res_gtags[r];
+        const unsigned w0 = S.res_off[r] >> 4, nw = (S.res_mask[r] + 1) >> 4;
+        for (unsigned q = t; q < nw; q += MO_THREADS) st_g16(dst + q, ((const uint4 *)B.tags)[w0 + q]);
+    }
+    return ok;
+}
+
 template <typename Rec, bool kResident = false, bool kCoop = false, bool kSeg = false>
 __global__ __launch_bounds__(MO_THREADS) __attribute__((amdgpu_waves_per_eu(4))) void k_merge_owned(const Rec *__restrict__ parts, int64_t slab,
                                                             const unsigned long long *__restrict__ SO, const unsigned *__restrict__ SP, int nseg,
@@ -270,6 +657,7 @@ __global__ __launch_bounds__(MO_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
                                                             unsigned seq, RowsOut rows, unsigned *bin_cnt, DevStats *st,
                                                             unsigned tag_bytes) {
     constexpr bool rehash = std::is_same<Rec, GrowRec>::value;
+    constexpr bool kEv = std::is_same<Rec, EventRec>::value;
     __shared__ MoShared S;
     extern __shared__ unsigned mo_tags[];   // tag_bytes of resident region tags
     __shared__ WinLds WL;
@@ -281,41 +669,15 @@ __global__ __launch_bounds__(MO_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
     const GenSink sink{gm};
     const int t = threadIdx.x;
     unsigned long long created_cnt = 0;
-    bool overflow = false;
+    bool overflow = false, hbm = false;
     for (int q = t; q < MO_CLAIM; q += MO_THREADS) S.claim[q] = 0;
     if (t == 0) S.n_touched = 0;
     __syncthreads();
     for (int bin = blockIdx.x; bin < nbins; bin += gridDim.x) {
         const int64_t b0 = (int64_t)O[(int64_t)bin * ntiles];
         const int64_t b1 = (int64_t)O[(int64_t)(bin + 1) * ntiles];   // (digit nbins: the gaps, after every bin)
-        // 0. the bin's resident regions: windows merged into this batch whose region maps to this bin
-        if (t == 0) {
-            int nr = 0;
-            unsigned off = 0;
-            if (!rehash && C.n >= 0 && b1 > b0) {
-                for (int q = 0; q < C.n; q++) {
-                    const GenDesc &g = C.e[q];
-                    if (!g.batch_parts) continue;
-                    const unsigned sb = g.sb, smask = (1u << sb) - 1;
-                    if (((unsigned)bin & smask) != (window_salt(g.wenc) & smask)) continue;
-                    const unsigned reg = ((unsigned)bin >> sb) - g.rbase;   // (a shard's table: its range only)
-                    if (reg >= (1u << g.rbits)) continue;
-                    const unsigned slots = (unsigned)g.rmask + 1;
-                    if (nr == MO_RES_MAX || off + slots > tag_bytes) continue;
-                    const unsigned long long first = (unsigned long long)reg << g.rshift;
-                    S.res_we[nr] = g.wenc;
-                    S.res_slots[nr] = g.tab + first;
-                    S.res_gtags[nr] = gen_tags(g) + first;
-                    S.res_off[nr] = off;
-                    S.res_mask[nr] = slots - 1;
-                    S.res_dirty[nr] = 0;
-                    S.res_new[nr] = 0;
-                    off += slots;
-                    nr++;
-                }
-            }
-            S.n_res = nr;
-        }
+        // 0. the bin's resident regions, their tags, the kSeg variant's segments
+        if (t == 0) mo_resident_regions(S, C, bin, !rehash && b1 > b0, tag_bytes);
         if constexpr (kSeg) {
             for (int q = t; q < nseg; q += MO_THREADS) {
                 seg_base[q] = SO[(int64_t)bin * nseg + q];
@@ -324,344 +686,19 @@ __global__ __launch_bounds__(MO_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
             if (t == 0) seg_pre[nseg] = (unsigned)(b1 - b0);
         }
         lds_barrier();
-        const int nres = S.n_res;
-        // the resident regions' tags (16-B words, regions >= 256 slots): every load of a thread in flight together
-        {
-            unsigned tot = 0;
-            for (int r = 0; r < nres; r++) tot += (S.res_mask[r] + 1) >> 4;
-            typedef __attribute__((address_space(1))) const hm_v4u gv4u;   // global loads (the pointers sit in LDS)
-            for (unsigned q0 = t; q0 < tot; q0 += 4 * MO_THREADS) {
-                uint4 v0, v1, v2, v3;
-                unsigned a0 = ~0u, a1 = ~0u, a2 = ~0u, a3 = ~0u;
-                auto fetch = [&](unsigned q, uint4 &v, unsigned &a) __attribute__((always_inline)) {
-                    if (q >= tot) return;
-                    unsigned w = q;
-                    int r = 0;
-                    while (w >= ((S.res_mask[r] + 1) >> 4)) { w -= (S.res_mask[r] + 1) >> 4; r++; }
-                    const hm_v4u x = ((gv4u *)S.res_gtags[r])[w];
-                    v = make_uint4(x.x, x.y, x.z, x.w);
-                    a = (S.res_off[r] >> 4) + w;
-                };
-                fetch(q0, v0, a0);
-                fetch(q0 + MO_THREADS, v1, a1);
-                fetch(q0 + 2 * MO_THREADS, v2, a2);
-                fetch(q0 + 3 * MO_THREADS, v3, a3);
-                if (a0 != ~0u) ((uint4 *)mo_tags)[a0] = v0;
-                if (a1 != ~0u) ((uint4 *)mo_tags)[a1] = v1;
-                if (a2 != ~0u) ((uint4 *)mo_tags)[a2] = v2;
-                if (a3 != ~0u) ((uint4 *)mo_tags)[a3] = v3;
-            }
-        }
+        const MoBin B{S, mo_tags, bin, b0, b1, S.n_res, seg_base, seg_pre, nseg};
+        mo_fill_tags(B, t);
         lds_barrier();
-        // find (and claim) the slot of lane t's key p, or join the lane of this chunk that holds it
-        auto probe = [&](const MRec &p, TileSlot *&gslot, bool &created, int &r, int &ci) __attribute__((always_inline)) {
-            unsigned long long *cl = S.claim;
-            const unsigned long long we = p.we;
-            const uint64_t hk = p.hk;
-            const unsigned tg = tag8(hk);
-            bool done = false;
-            r = -1;
-            for (int q = 0; q < nres; q++)
-                if (S.res_we[q] == we) r = q;
-            if (r >= 0) {
-                const unsigned rmask = S.res_mask[r], off = S.res_off[r];
-                TileSlot *const base = S.res_slots[r];
-                unsigned s = (unsigned)inreg_slot(hk, rmask);
-                // Tags scanned 8 at a time (one 8-B LDS read): only slots whose tag is empty or this key's are visited
-                // one by one, so a wave's loop runs its lanes' longest count of such slots, not of probed slots.
-                // (regions are >= 256 slots and start at multiples of their size: a word never crosses a region)
-                const unsigned long long tgv = (unsigned long long)tg * UINT64_C(0x0101010101010101);
-                const unsigned long long *tags64 = (const unsigned long long *)mo_tags;
-                for (unsigned scanned = 0; scanned <= rmask && !done;) {
-                    const unsigned bw = off + s, p0 = bw & 7;
-                    const unsigned long long word = __hip_atomic_load(&tags64[bw >> 3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    // high bit of each byte that is 0 (exact per byte: no borrow between bytes), or equal to tg
-                    constexpr unsigned long long LO7 = UINT64_C(0x7f7f7f7f7f7f7f7f);
-                    const unsigned long long y = word ^ tgv;
-                    unsigned long long cand = ~(((word & LO7) + LO7) | word | LO7) | ~(((y & LO7) + LO7) | y | LO7);
-                    cand &= ~UINT64_C(0) << (8 * p0);
-                    if (!cand) {   // no candidate in the rest of the word: the next word
-                        scanned += 8 - p0;
-                        s = (s + 8 - p0) & rmask;
-                        continue;
-                    }
-                    const unsigned pos = (unsigned)__builtin_ctzll(cand) >> 3;
-                    scanned += pos - p0 + 1;
-                    s = (s + pos - p0) & rmask;
-                    TileSlot *const sl = base + s;
-                    const unsigned long long addr = (unsigned long long)sl;
-                    const unsigned bi = off + s, sh = (bi & 3) * 8;
-                    const unsigned b = (unsigned)(word >> (8 * pos)) & 0xffu;
-                    {
-                        unsigned *const cl32 = (unsigned *)cl;
-                        int x = b == 0 ? -1 : kResident ? mo_holder32(cl32, bi) : mo_holder(cl, addr);
-                        bool old_match = false;
-                        if (b == tg && x < 0) old_match = ld_l2(&sl->cell) == p.cell && ld_l2(&sl->wenc) == we;
-                        if (b == 0 || old_match) {
-                            x = kResident ? mo_claim32(cl32, bi, t, ci) : mo_claim(cl, addr, t, ci);
-                            if (x == -1) {
-                                gslot = sl;
-                                created = b == 0;
-                                if (created) {
-                                    atomicOr(&mo_tags[bi >> 2], tg << sh);
-                                    S.res_dirty[r] = 1;
-                                }
-                                done = true;
-                            }
-                        }
-                        if (!done && x >= 0 && S.sc[x] == p.cell && S.sh[x] == hk) {   // same key, this chunk
-                            mo_add_into(S, x, p);
-                            done = true;
-                        }
-                    }
-                    s = (s + 1) & rmask;
-                }
-            } else if constexpr (!kResident) {
-                const GenDesc *g = gen_lookup(C, gm, we);
-                if (g) {
-                    TileSlot *const tab = g->tab;
-                    const unsigned long long rmask = g->rmask;
-                    unsigned long long sidx = home_slot(*g, hk);
-                    for (unsigned long long pr = 0; pr <= rmask && !done; pr++) {
-                        TileSlot *const sl = &tab[sidx];
-                        const unsigned long long addr = (unsigned long long)sl;
-                        const bool free_here = ld_l2(&sl->wenc) != we;   // never used, or another window's key
-                        if (free_here || ld_l2(&sl->cell) == p.cell) {
-                            const int x = mo_claim(cl, addr, t, ci);
-                            if (x == -1) {
-                                gslot = sl;
-                                created = free_here;
-                                if (created) ((__attribute__((address_space(1))) uint8_t *)gen_tags(*g))[sidx] = (uint8_t)tag8(hk);
-                                done = true;
-                            } else if (S.sc[x] == p.cell && S.sh[x] == hk) {
-                                mo_add_into(S, x, p);
-                                done = true;
-                            }
-                        }
-                        sidx = next_slot(sidx, rmask);
-                    }
-                }
-            }
-            if (!done) overflow = true;
-        };
-        // The resident-only merge's probe, wave-cooperative: each round every lane still probing scans its region's
-        // tags to its next candidate slot (empty or its tag); the lanes whose candidate holds an older key of the same
-        // tag then load those lines TOGETHER, whole (lane L loads part L & 3 of the line of lane 16k + L / 4, 16 lines
-        // per 16-B instruction, through the wave's LDS scratch), compare the key and keep the line: one round trip per
-        // existing key, and no second load of the line after the barrier.
-        auto probe_coop = [&](const MRec &p, bool has, TileSlot *&gslot, bool &created, int &r, int &ci, MLine &pre,
-                              bool &preloaded) __attribute__((always_inline)) {
-            unsigned *const cl32 = (unsigned *)S.claim;
-            const unsigned long long we = p.we;
-            const uint64_t hk = p.hk;
-            const unsigned tg = tag8(hk);
-            r = -1;
-            if (has)
-                for (int q = 0; q < nres; q++)
-                    if (S.res_we[q] == we) r = q;
-            bool done = !has || r < 0, lost = has && r < 0;
-            unsigned rmask = 0, off = 0, s = 0, scanned = 0;
-            TileSlot *base = nullptr;
-            if (r >= 0) {
-                rmask = S.res_mask[r];
-                off = S.res_off[r];
-                base = S.res_slots[r];
-                s = (unsigned)inreg_slot(hk, rmask);
-            }
-            const unsigned long long tgv = (unsigned long long)tg * UINT64_C(0x0101010101010101);
-            const unsigned long long *tags64 = (const unsigned long long *)mo_tags;
-            uint4 *xa = &S.xline[t >> 6][0], *xb = &S.xline[t >> 6][32];
-            const int ln = lane_id();
-            while (__ballot(!done)) {
-                // 1. this lane's next candidate slot
-                unsigned b = 0;
-                bool found = false;
-                if (!done) {
-                    while (scanned <= rmask) {
-                        const unsigned bw = off + s, p0 = bw & 7;
-                        const unsigned long long word = __hip_atomic_load(&tags64[bw >> 3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        constexpr unsigned long long LO7 = UINT64_C(0x7f7f7f7f7f7f7f7f);
-                        const unsigned long long y = word ^ tgv;
-                        unsigned long long cand = ~(((word & LO7) + LO7) | word | LO7) | ~(((y & LO7) + LO7) | y | LO7);
-                        cand &= ~UINT64_C(0) << (8 * p0);
-                        if (!cand) {
-                            scanned += 8 - p0;
-                            s = (s + 8 - p0) & rmask;
-                            continue;
-                        }
-                        const unsigned pos = (unsigned)__builtin_ctzll(cand) >> 3;
-                        scanned += pos - p0 + 1;
-                        s = (s + pos - p0) & rmask;
-                        b = (unsigned)(word >> (8 * pos)) & 0xffu;
-                        found = true;
-                        break;
-                    }
-                    if (!found) { done = true; lost = true; }   // the region is full
-                }
-                const unsigned bi = off + s;
-                TileSlot *const sl = base + s;
-                // 2. a tag-matching slot: claimed in this chunk (its holder), else its line from HBM, loaded together
-                int x = -1;
-                if (found && b != 0) x = mo_holder32(cl32, bi);
-                const bool need = found && b == tg && x < 0;
-                hm_v4u q0{}, q1{}, q2{}, q3{};
-                const unsigned long long ga = need ? (unsigned long long)sl : 0ull;
-                const unsigned long long needm = __ballot(need);
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    if (!((needm >> (16 * k)) & 0xffffull)) continue;   // (wave-uniform)
-                    const int src = k * 16 + (ln >> 2), part = ln & 3;
-                    const unsigned long long sa = __shfl(ga, src, 64);
-                    if (sa) {
-                        const hm_v4u v = __builtin_nontemporal_load((g_cv4u *)sa + part);
-                        ((part < 2) ? xa : xb)[(src & 15) * 2 + (part & 1)] = make_uint4(v.x, v.y, v.z, v.w);
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    if (need && (ln >> 4) == k) {
-                        const int e = (ln & 15) * 2;
-                        const uint4 a0 = xa[e], a1 = xa[e + 1], a2 = xb[e], a3 = xb[e + 1];
-                        q0 = hm_v4u{a0.x, a0.y, a0.z, a0.w};
-                        q1 = hm_v4u{a1.x, a1.y, a1.z, a1.w};
-                        q2 = hm_v4u{a2.x, a2.y, a2.z, a2.w};
-                        q3 = hm_v4u{a3.x, a3.y, a3.z, a3.w};
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                }
-                const bool old_match = need && ((unsigned long long)q0.x | ((unsigned long long)q0.y << 32)) == p.cell &&
-                                       ((unsigned long long)q0.z | ((unsigned long long)q0.w << 32)) == we;
-                // 3. claim an empty slot or the key's own
-                if (found && (b == 0 || old_match)) {
-                    x = mo_claim32(cl32, bi, t, ci);
-                    if (x == -1) {
-                        gslot = sl;
-                        created = b == 0;
-                        if (created) {
-                            atomicOr(&mo_tags[bi >> 2], tg << ((bi & 3) * 8));
-                            S.res_dirty[r] = 1;
-                        } else {
-                            pre.count = (unsigned long long)q1.x | ((unsigned long long)q1.y << 32);
-                            pre.nspeed = (unsigned long long)q1.z | ((unsigned long long)q1.w << 32);
-                            pre.sspeed = __builtin_bit_cast(double, (unsigned long long)q2.x | ((unsigned long long)q2.y << 32));
-                            pre.slat = __builtin_bit_cast(double, (unsigned long long)q2.z | ((unsigned long long)q2.w << 32));
-                            pre.slon = __builtin_bit_cast(double, (unsigned long long)q3.x | ((unsigned long long)q3.y << 32));
-                            pre.touched = (unsigned long long)q3.z | ((unsigned long long)q3.w << 32);
-                            preloaded = true;
-                        }
-                        done = true;
-                    }
-                }
-                if (found && !done && x >= 0 && S.sc[x] == p.cell && S.sh[x] == hk) {   // same key, this chunk
-                    mo_add_into(S, x, p);
-                    done = true;
-                }
-                if (found && !done) s = (s + 1) & rmask;
-            }
-            if (lost) overflow = true;
-        };
-        // the new state line of a claimed slot (old values read here: the slot's last store is visible) and its
-        // update-mode row index
-        // the slot's current line (all loads of a lane issued together; created slots read nothing)
-        auto old_line = [&](TileSlot *gslot, bool created, const MLine &pre, bool preloaded) __attribute__((always_inline)) -> MLine {
-            MLine o{};
-            if (preloaded) o = pre;
-            created = created || preloaded;   // (the probe loaded it: nothing to load here)
-            // whole lines per load instruction (the mirror of step 4's stores): in round k, lane L loads part L & 3 of
-            // the line of lane 16k + L / 4 (16-B non-temporal loads: L2-served, like ld_l2) into the wave's LDS slice,
-            // and lanes 16k..16k+15 take their lines from there.  Every lane of the wave runs it (shuffles).
-            const bool need = gslot && !created;
-            if (__ballot(need)) {
-                // (its own scratch: the lines are loaded before the barrier, while other waves' joiners still read
-                // this wave's staged keys in S.sc / S.sh)
-                uint4 *xa = &S.xline[t >> 6][0], *xb = &S.xline[t >> 6][32];
-                const int ln = lane_id();
-                const unsigned long long ga = need ? (unsigned long long)gslot : 0ull;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const int src = k * 16 + (ln >> 2), part = ln & 3;
-                    const unsigned long long sa = __shfl(ga, src, 64);
-                    if (sa) {
-                        const hm_v4u x = __builtin_nontemporal_load((g_cv4u *)sa + part);
-                        ((part < 2) ? xa : xb)[(src & 15) * 2 + (part & 1)] = make_uint4(x.x, x.y, x.z, x.w);
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    if (need && (ln >> 4) == k) {
-                        const int e = (ln & 15) * 2;
-                        const uint4 q1 = xa[e + 1], q2 = xb[e], q3 = xb[e + 1];   // (part 0: cell, window)
-                        o.count = (unsigned long long)q1.x | ((unsigned long long)q1.y << 32);
-                        o.nspeed = (unsigned long long)q1.z | ((unsigned long long)q1.w << 32);
-                        o.sspeed = __builtin_bit_cast(double, (unsigned long long)q2.x | ((unsigned long long)q2.y << 32));
-                        o.slat = __builtin_bit_cast(double, (unsigned long long)q2.z | ((unsigned long long)q2.w << 32));
-                        o.slon = __builtin_bit_cast(double, (unsigned long long)q3.x | ((unsigned long long)q3.y << 32));
-                        o.touched = (unsigned long long)q3.z | ((unsigned long long)q3.w << 32);
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                }
-            }
-            return o;
-        };
-        auto line_of = [&](const MRec &p, const MLine &o, bool first, unsigned krow) __attribute__((always_inline)) -> MLine {
-            MLine v;
-            const unsigned long long acnt = S.scnt[t], ansp = S.snsp[t];
-            v.count = o.count + acnt;
-            v.nspeed = o.nspeed + ansp;
-            v.sspeed = ansp ? o.sspeed + S.sssp[t] : o.sspeed;
-            v.slat = o.slat + S.sslat[t];
-            v.slon = o.slon + S.sslon[t];
-            if constexpr (rehash) v.touched = p.touched;
-            else v.touched = first ? ((unsigned long long)seq << 32) | krow : o.touched;
-            return v;
-        };
-        // row index of a key's first touch in this batch: one LDS add per wave
-        auto touch_rows = [&](bool first) __attribute__((always_inline)) -> unsigned {
-            const unsigned long long fb = __ballot(first);
-            unsigned tbase = 0;
-            if (lane_id() == 0 && fb) tbase = atomicAdd(&S.n_touched, (unsigned)__popcll(fb));
-            tbase = __shfl(tbase, 0, 64);
-            return tbase + (unsigned)__popcll(fb & ((1ull << lane_id()) - 1));
-        };
-        // (one LDS add per created key: a ballot per resident region measured 0.17 ms slower on the bench, r4j/)
-        auto count_created = [&](bool created, int r) __attribute__((always_inline)) {
-            if (created && r >= 0) atomicAdd(&S.res_new[r], 1u);
-        };
         // software pipeline: the next chunk's record is loaded while this chunk is merged
         Rec nxt;
         // the bin's records: [b0, b1) of the partitioned array, or (slab != 0: k_ingest's fused binning) the first
         // b1 - b0 records of the bin's slab; either way row k of the bin goes to b0 + k
         const Rec *__restrict__ bp = slab ? parts + ((int64_t)bin * slab - b0) : parts;
-        // kSeg: the record at bin index v = i - b0 is in the last segment starting at or before v (binary search)
-        auto rec_at = [&](int64_t i) __attribute__((always_inline)) -> const Rec * {
-            if constexpr (kSeg) {
-                const unsigned v = (unsigned)(i - b0);
-                int lo = 0, hi = nseg;   // seg_pre[lo] <= v < seg_pre[hi]
-                while (hi - lo > 1) {
-                    const int mid = (lo + hi) >> 1;
-                    if (seg_pre[mid] <= v) lo = mid; else hi = mid;
-                }
-                const Rec *rp = (const Rec *)(uintptr_t)seg_base[lo] + (v - seg_pre[lo]);
-#if MOBHEAT_BOUNDS_CHECK
-                const unsigned long long a = (unsigned long long)(uintptr_t)rp, e = a + sizeof(Rec);
-                const SegBounds &B = g_seg_bounds;
-                if (!((a >= B.lo[0] && e <= B.hi[0]) || (a >= B.lo[1] && e <= B.hi[1]))) {
-                    printf("k_merge_owned: bin %d segment %d record %u at 0x%llx outside [0x%llx, 0x%llx) and [0x%llx, 0x%llx)\n",
-                           bin, lo, v, a, B.lo[0], B.hi[0], B.lo[1], B.hi[1]);
-                    __builtin_trap();
-                }
-#endif
-                return rp;
-            } else {
-                return bp + i;
-            }
-        };
-        constexpr bool kEv = std::is_same<Rec, EventRec>::value;
         // EventRec: the next chunk's window parameters are loaded with the chunk's store drain, so that the record's
         // hash needs no dependent load at the chunk's start (state-read leg's merge -0.27 ms, bench leg unchanged:
         // profiles/r4/r4v7/)
         WInfo nwi{};
-        if (b0 + t < b1) nxt = ld_stream(rec_at(b0 + t));
+        if (b0 + t < b1) nxt = ld_stream(mo_rec_at<Rec, kSeg>(B, bp, b0 + t));
         if constexpr (kEv) { if (b0 + t < b1) nwi = winfo[ekey_widx(nxt.key)]; }
         for (int64_t c0 = b0; c0 < b1; c0 += MO_THREADS) {
             // 1. stage this chunk's records in LDS
@@ -672,72 +709,34 @@ __global__ __launch_bounds__(MO_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
                 if constexpr (kEv) p = mrec_of_wi(nxt, nwi, cell_hi);
                 else p = mrec_of(nxt, winfo, cell_hi);
             }
-            if (i + MO_THREADS < b1) nxt = ld_stream(rec_at(i + MO_THREADS));
-            if (has) {
-                S.sc[t] = p.cell;
-                S.sh[t] = p.hk;
-                S.scnt[t] = p.cnt;
-                S.snsp[t] = p.nsp;
-                S.sssp[t] = p.ssp;
-                S.sslat[t] = p.slat;
-                S.sslon[t] = p.slon;
-            }
+            if (i + MO_THREADS < b1) nxt = ld_stream(mo_rec_at<Rec, kSeg>(B, bp, i + MO_THREADS));
+            if (has) mo_stage(S, t, p);
             lds_barrier();
             // 2. find and claim the key's slot, or join the lane that holds it
-            TileSlot *gslot = nullptr;
-            bool created = false, preloaded = false;
-            int r = -1, ci = -1;
-            MLine pre{};
-            if constexpr (kResident && kCoop) probe_coop(p, has, gslot, created, r, ci, pre, preloaded);
-            else if (has) probe(p, gslot, created, r, ci);
-            count_created(created, r);
+            MoProbe pr;
+            if constexpr (kResident && kCoop) mo_probe_coop(B, p, has, t, pr);
+            else if (has) mo_probe<kResident>(B, C, gm, p, t, pr);
+            overflow |= pr.lost;
+            hbm |= pr.hbm;
+            TileSlot *const gslot = pr.gslot;
+            const bool created = pr.created;
+            // (one LDS add per created key: a ballot per resident region measured 0.17 ms slower on the bench, r4j/)
+            if (created && pr.r >= 0) atomicAdd(&S.res_new[pr.r], 1u);
             // 3a. the claimed existing lines, loaded before the barrier (their slots' last stores were drained by an
             // earlier chunk's barrier, and no store of this chunk precedes step 4): the round trip overlaps the wait
-            const MLine o = old_line(gslot, created, pre, preloaded);
+            const MLine o = mo_old_line(S, t, pr);
             lds_barrier();
-            // 3. the claimers' new lines
+            // 3. the claimers' new lines (old values read above: the slot's last store is visible) and row indices
             MLine v{};
             const bool retouch = !rehash && gslot && !created && (unsigned)(o.touched >> 32) == seq;
             const bool first = !rehash && gslot && !retouch;
             // (the row index is absolute -- the bin's first row b0 + its touch order -- so that a later merge of the same
             // batch, whose segment of the bin starts elsewhere, rewrites the row in place: a pipelined batch's chunks)
-            unsigned krow = (unsigned)b0 + touch_rows(first);
+            unsigned krow = (unsigned)b0 + mo_touch_rows(S, first);
             if (!first) krow = (unsigned)o.touched;
-            if (gslot) v = line_of(p, o, first, krow);
+            if (gslot) v = mo_new_line<rehash>(S, t, p, o, first, seq, krow);
             // 4. this chunk's stores: the state line (whole) and the key's row
-            {
-                const uint64_t b0s = __builtin_bit_cast(uint64_t, v.sspeed), b1s = __builtin_bit_cast(uint64_t, v.slat);
-                const uint64_t b2s = __builtin_bit_cast(uint64_t, v.slon);
-                const uint4 q0 = make_uint4((unsigned)p.cell, (unsigned)(p.cell >> 32), (unsigned)p.we, (unsigned)(p.we >> 32));
-                const uint4 q1 = make_uint4((unsigned)v.count, (unsigned)(v.count >> 32), (unsigned)v.nspeed, (unsigned)(v.nspeed >> 32));
-                const uint4 q2 = make_uint4((unsigned)b0s, (unsigned)(b0s >> 32), (unsigned)b1s, (unsigned)(b1s >> 32));
-                const uint4 q3 = make_uint4((unsigned)b2s, (unsigned)(b2s >> 32), (unsigned)v.touched, (unsigned)(v.touched >> 32));
-                // whole lines per store instruction: in round k, the wave's lanes 16k..16k+15 put their lines in LDS
-                // (the wave's slices of S.sc / S.sh, unused after the probe), then lane L stores part L & 3 of line
-                // 16k + L / 4 -- each 16-B store instruction writes 16 whole 64-B lines instead of a quarter of 64
-                // (each lane's own line: four instructions, each touching 64 different lines)
-                uint4 *xa = (uint4 *)&S.sc[t & ~63], *xb = (uint4 *)&S.sh[t & ~63];
-                const int ln = lane_id();
-                const unsigned long long ga = (unsigned long long)gslot;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    if ((ln >> 4) == k) {
-                        const int e = (ln & 15) * 2;
-                        xa[e] = q0;
-                        xa[e + 1] = q1;
-                        xb[e] = q2;
-                        xb[e + 1] = q3;
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    const int src = k * 16 + (ln >> 2), part = ln & 3;
-                    const unsigned long long sa = __shfl(ga, src, 64);
-                    const uint4 val = ((part < 2) ? xa : xb)[(src & 15) * 2 + (part & 1)];
-                    if (sa) st_g16((uint4 *)sa + part, val);
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                }
-            }
+            mo_store_lines(S, t, gslot, p, v);
             if (gslot) {
                 if (created) created_cnt++;
                 if (!rehash) put_row(rows, (int64_t)krow, p.cell, p.we, v.count, v.nspeed, v.sspeed, v.slat, v.slon);
@@ -745,7 +744,7 @@ __global__ __launch_bounds__(MO_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
             // created keys of non-resident windows count for their window here (resident ones: res_new); rehash:
             // the host already carries the moved keys
             if constexpr (!kResident) {
-                const bool count_here = created && !rehash && r < 0;
+                const bool count_here = created && !rehash && pr.r < 0;
                 if (__ballot(count_here) && !wave_count_windows(count_here, p.we, 1ull, WL, sink)) overflow = true;
             }
             if constexpr (kEv) { if (i + MO_THREADS < b1) nwi = winfo[ekey_widx(nxt.key)]; }
@@ -753,20 +752,11 @@ __global__ __launch_bounds__(MO_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
             // the wave -- measured: draining them a chunk later instead, deferring the keys the previous chunk wrote,
             // cost 1.5 ms on the bench and 4.5 ms on the state-read leg); release the claims
             __syncthreads();
-            if (ci >= 0) {
-                if constexpr (kResident) ((unsigned *)S.claim)[ci] = 0u;
-                else S.claim[ci] = 0;
-            }
+            if (pr.ci >= 0) MoClaimsOf<kResident>{(typename MoClaimsOf<kResident>::Key *)S.claim}.release(pr.ci);
         }
         lds_barrier();
         // 6. write the resident regions' tags back
-        if (t < nres && S.res_new[t] && !gmap_add(gm, S.res_we[t], S.res_new[t])) overflow = true;
-        for (int r = 0; r < nres; r++) {
-            if (!S.res_dirty[r]) continue;
-            uint4 *dst = (uint4 *)S.res_gtags[r];
-            const unsigned w0 = S.res_off[r] >> 4, nw = (S.res_mask[r] + 1) >> 4;
-            for (unsigned q = t; q < nw; q += MO_THREADS) st_g16(dst + q, ((const uint4 *)mo_tags)[w0 + q]);
-        }
+        if (!mo_tags_writeback(B, gm, t)) overflow = true;
         if (t == 0) { bin_cnt[bin] = S.n_touched; S.n_touched = 0; }
         lds_barrier();
     }
@@ -777,10 +767,12 @@ __global__ __launch_bounds__(MO_THREADS) __attribute__((amdgpu_waves_per_eu(4)))
         if (created_cnt) atomicAdd(&st->n_state_new, created_cnt);
         if (ov) atomicAdd(&st->overflow, 1ull);
     }
+    // (hm_last_counts [12], bit 8: once per wave that had a record probe through HBM; growth always does, uncounted)
+    if constexpr (!kResident && !rehash) { if (__ballot(hbm) && lane_id() == 0) atomicAdd(&st->merge_hbm, 1ull); }
 }
 
 // =====================================================================================================
-// K4: close the gaps between the bins' row segments: bin b's rows [O(b), O(b) + cnt[b]) -> [off[b], ...)
+// Housekeeping kernels of a batch: zeroing released window tables' tags, the start-of-batch reset
 // =====================================================================================================
 // zero n16 16-B words (the window tables' tag bytes on pool reuse: hipMemsetAsync's fill kernel ran at ~0.3 TB/s
 // on these 64-MB ranges, 0.68 ms per batch)
@@ -816,6 +808,9 @@ __global__ __launch_bounds__(256) void k_batch_reset(unsigned long long *__restr
     if (i == 0) { *slow_word = 0; *giveup_word = 0; }
 }
 
+// =====================================================================================================
+// K4: close the gaps between the bins' row segments: bin b's rows [O(b), O(b) + cnt[b]) -> [off[b], ...)
+// =====================================================================================================
 // In-place densification of the per-bin row segments: bin b's merged rows are [s_b, s_b + c_b) of the staging
 // arrays (s_b = the bin's first partial, c_b its touched keys), so the rows [0, T) (T = sum c_b) are dense except
 // for the gaps left by keys with several partials; each gap below T takes one row from above T (gap i <- the i-th

@@ -189,6 +189,8 @@ struct DevStats {
     unsigned long long n_partials;
     unsigned long long n_touched;
     unsigned long long n_state_new; // keys created in the state tables
+    unsigned long long merge_hbm;   // k_merge_owned workgroups with a record of a window not resident in LDS, probed
+                                    // through HBM (hm_last_counts [12], bit 8; growth's rehash merges are not counted)
     unsigned long long n_dedup_used;
     unsigned long long n_cands;
     unsigned long long overflow;    // nonzero: a hash table probe bound was exceeded

@@ -283,9 +283,10 @@ def test_dedup_more_vehicles_than_fused_table(dense, monkeypatch):
 
 def test_merge_many_duplicate_keys_per_chunk():
     """Every key of a 6M-row binned batch occurs 4 times (1.5M keys, ~183 per bin, one window): a merge chunk of 512
-    records holds more keys with in-chunk duplicates than k_merge_owned's joiner accumulator pool (MO_ACC = 128), so
-    the joiners left over wait for a second pass of the chunk.  Counts and averages against the oracle, then the same
-    keys again in a second batch (every key existing)."""
+    records holds well over a hundred keys with in-chunk duplicates, whose later lanes find the key's slot claimed in
+    the chunk's claim set and add their values into the claimer's staging entry in LDS (k_merge.h: mo_probe,
+    mo_add_into).  Counts and averages against the oracle, then the same keys again in a second batch (every key
+    existing)."""
     from mobheat import HeatmapEngine
     from oracle.spark_oracle import SparkHeatmapOracle
     rng = np.random.default_rng(77)
@@ -581,9 +582,9 @@ def test_ingest_modes_parity(mode, monkeypatch):
 @pytest.mark.parametrize("mode", ["direct", "binned", "binned_whole"])
 def test_direct_merge_keys_repeated_across_chunks(mode, monkeypatch):
     """k_merge_owned with every key in several consecutive 512-record chunks of its bin (direct path forced: 1.2e7 rows
-    over ~5e5 res-11 keys, ~1.5k rows per bin): a chunk's stores are only drained by the next chunk's full barrier, so
-    a key the previous chunk wrote is deferred behind it (mobheat.hip: k_merge_owned step 4) -- counts and sums must
-    still add up exactly; a second batch in the same window re-reads every key's state."""
+    over ~5e5 res-11 keys, ~1.5k rows per bin): every chunk ends with a full barrier that drains its stores (k_merge.h:
+    k_merge_owned step 5), so the next chunk reads the line the previous one wrote for the same key -- counts and sums
+    must still add up exactly; a second batch in the same window re-reads every key's state."""
     from mobheat import HeatmapEngine, synth
     from oracle.spark_oracle import SparkHeatmapOracle
     monkeypatch.setenv("MOBHEAT_SUBBINS", "0" if mode == "binned_whole" else "1")
