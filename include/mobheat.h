@@ -32,6 +32,7 @@
  *                                   newest position so far, folded across batches on the device.
  *   hm_window_geojson / hm_positions_geojson -- the two endpoints' response bodies (app.py:45-88) as GeoJSON encoded on
  *                                   the GPU, byte for byte json.dumps of the collections the reference builds in Python.
+ *   hm_window_geojson_view / hm_positions_geojson_view / hm_cells_in_view -- the same for a client's map viewport.
  */
 #ifndef MOBHEAT_H
 #define MOBHEAT_H
@@ -575,8 +576,38 @@ int hm_selftest_position_features(const hm_position_doc_cfg *cfg, const hm_posit
                                   int64_t cap, int64_t *offsets);
 /* up to n of, for the last GeoJSON call on the context (HIP events): [0] its sizes kernel (for tiles: the boundaries
  * included), microseconds, [1] its write kernel, [2] from the first kernel to the last, the offsets' scan and its
- * read-back included, [3] the body's length in bytes. */
+ * read-back included, [3] the body's length in bytes, [4] the candidates of the last hm_*_geojson_view call (the roll-up's
+ * records, or the positions state's keys), [5] that call's filter kernel, microseconds. */
 int hm_geojson_info(const hm_ctx *ctx, int64_t *v, int32_t n);
+
+/* ---- the same bodies for a map viewport (a Leaflet client's bbox), filtered on the GPU ----
+ * A view is (west, south, east, north) in degrees, valid when all four are finite, -90 <= south <= north <= 90 and
+ * -180 <= west, east <= 180; its longitudes are [west, east], or [west, 180] U [-180, east] when west > east (the view
+ * crosses the antimeridian).  Every interval is closed and every test a plain binary64 comparison: no tolerance.
+ *   position  in view iff south <= lat <= north and lon is one of the view's longitudes (the stored doubles).
+ *   tile      in view iff the latitude-longitude box of its boundary ring (hm_cells_to_boundary's vertices) meets the
+ *             view: latitudes [min lat, max lat]; longitudes [min lng, max lng], unless max lng - min lng > 180 -- the
+ *             ring wraps: [min of the lng > 0, 180] U [-180, max of the lng <= 0].  The two cells of a resolution that
+ *             contain a pole (latLngToCell(+-90, 0, res)) cover every longitude and latitudes up to their pole.  An
+ *             invalid index (0 vertices) is never in view.  "Meets": the latitude ranges intersect and an interval of
+ *             one longitude set intersects an interval of the other.
+ * An invalid view: HM_E_INVALID, nothing touched. */
+typedef struct { double west, south, east, north; } hm_view;
+/* keep_u8[i] = 1 iff cells[i] is in view (cells of any mix of resolutions; memory / device as hm_cells_to_boundary:
+ * with HM_MEM_DEVICE cells and keep_u8 are device pointers) */
+int hm_cells_in_view(const uint64_t *cells, int64_t n, int32_t memory, int32_t device, const hm_view *view, uint8_t *keep_u8);
+/* Host execution of the same code (no GPU). */
+int hm_selftest_cells_in_view(const uint64_t *cells, int64_t n, const hm_view *view, uint8_t *keep_u8);
+/* hm_window_geojson of the tiles in view: roll up, filter, encode the kept records; *n = the kept count, recs (optional)
+ * the kept records in feature order; none kept: the 42-byte empty body.  hm_window_geojson's errors, and HM_E_INVALID
+ * for an invalid view.  On a shard context: the rank's own keys, as hm_window_rollup.  Reads only, as hm_window_geojson;
+ * a repeated call allocates nothing. */
+int hm_window_geojson_view(hm_ctx *ctx, int64_t window_start_us, int32_t res, const hm_geojson_cfg *cfg, int32_t out_memory,
+                           const uint8_t **bytes, const int64_t **offsets, int64_t *n, const hm_state_rec **recs,
+                           const hm_view *view);
+/* hm_positions_geojson of the positions in view (*n = the kept count); its errors, and HM_E_INVALID for an invalid view */
+int hm_positions_geojson_view(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t out_memory, const uint8_t **bytes,
+                              const int64_t **offsets, int64_t *n, const hm_position_rec **recs, const hm_view *view);
 
 /* json.dumps(x) of n doubles -- CPython's float.__repr__, NaN / Infinity / -Infinity for the non-finite -- as the GeoJSON
  * encoders write them (csrc/float_repr.h), executed on the host and on GPU `device` (test entry points): value i's

@@ -20,6 +20,7 @@ static int gj_init(hm_ctx *ctx) {
     int rc;
     if ((rc = ensure(ctx, G.words, GJW_WORDS * 8))) return rc;
     for (auto &e : G.ev) HIPCHK(ctx, hipEventCreate(&e));
+    for (auto &e : G.vev) HIPCHK(ctx, hipEventCreate(&e));
     G.ready = true;
     return HM_OK;
 }
@@ -228,14 +229,15 @@ int hm_positions_buckets(hm_ctx *ctx, int64_t *bucket_ids, int64_t cap, int64_t 
     return HM_OK;
 }
 
-int hm_positions_geojson(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t out_memory, const uint8_t **bytes,
-                         const int64_t **offsets, int64_t *n, const hm_position_rec **recs) {
+// hm_positions_geojson (view nullptr: the whole state) and hm_positions_geojson_view (api_view.h: the valid view's part)
+static int gj_positions(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t out_memory, const uint8_t **bytes,
+                        const int64_t **offsets, int64_t *n, const hm_position_rec **recs, const hm_view *view, const char *who) {
     if (!ctx || !buckets || !bytes || !offsets || !n || (out_memory != HM_MEM_HOST && out_memory != HM_MEM_DEVICE))
         return ctx ? set_err(ctx, HM_E_INVALID, "bad argument") : HM_E_INVALID;
     if (ctx->shard_count > 1)
-        return set_err(ctx, HM_E_UNSUPPORTED, "hm_positions_geojson on shard %d of %d: a rank holds only the latest rows it received",
+        return set_err(ctx, HM_E_UNSUPPORTED, "%s on shard %d of %d: a rank holds only the latest rows it received", who,
                        ctx->shard_rank, ctx->shard_count);
-    if (ctx->stage != 0) return set_err(ctx, HM_E_STATE, "hm_positions_geojson between stage calls");
+    if (ctx->stage != 0) return set_err(ctx, HM_E_STATE, "%s between stage calls", who);
     int rc;
     if ((rc = gj_buckets_ok(ctx, buckets))) return rc;
     hm_ctx::Positions &P = ctx->pos;
@@ -244,7 +246,11 @@ int hm_positions_geojson(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_
     if (recs) *recs = nullptr;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if ((rc = gj_init(ctx))) return rc;
-    const int64_t m = P.tab ? P.keys : 0;
+    int64_t m = P.tab ? P.keys : 0;
+    if (view) {
+        G.candidates = m;
+        G.view_us = 0;
+    }
     if (m == 0) {
         if ((rc = gj_empty(ctx))) return rc;
         return gj_out(ctx, 0, (int64_t)sizeof(GJ_EMPTY_BODY) - 1, out_memory, bytes, offsets);
@@ -260,8 +266,27 @@ int hm_positions_geojson(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_
         HIPCHK(ctx, hipMemcpyAsync((int64_t *)G.params.p + nb, buckets->bucket_offset_s, (size_t)nb * 8, hipMemcpyHostToDevice, ctx->stream));
     }
     // the state's records in feature order (k_pos_emit's compaction, into a buffer of this call's own)
-    hipLaunchKernelGGL(k_pos_emit, dim3(grid_for((int64_t)P.cap, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, (const PosSlot *)P.tab,
-                       (int64_t)P.cap, (hm_position_rec *)G.precs.p, m, words + GJW_OUT);
+    if (!view) {
+        hipLaunchKernelGGL(k_pos_emit, dim3(grid_for((int64_t)P.cap, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, (const PosSlot *)P.tab,
+                           (int64_t)P.cap, (hm_position_rec *)G.precs.p, m, words + GJW_OUT);
+    } else {   // the same compaction with the point test; the features run over what it kept
+        unsigned long long kept = 0;
+        HIPCHK(ctx, hipEventRecord(G.vev[0], ctx->stream));
+        hipLaunchKernelGGL(k_pos_emit_view, dim3(grid_for((int64_t)P.cap, 256 * DUMP_PER)), dim3(256), 0, ctx->stream,
+                           (const PosSlot *)P.tab, (int64_t)P.cap, *view, (hm_position_rec *)G.precs.p, m, words + GJW_OUT);
+        HIPCHK(ctx, hipEventRecord(G.vev[1], ctx->stream));
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(&kept, words + GJW_OUT, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, ctx_sync(ctx, __LINE__));
+        float vms = 0;
+        if (hipEventElapsedTime(&vms, G.vev[0], G.vev[1]) == hipSuccess) G.view_us = 1e3 * vms;
+        if ((int64_t)kept > m) return set_err(ctx, HM_E_STATE, "positions state holds %llu keys, at most %lld expected", kept, (long long)m);
+        m = (int64_t)kept;
+        if (m == 0) {
+            if ((rc = gj_empty(ctx))) return rc;
+            return gj_out(ctx, 0, (int64_t)sizeof(GJ_EMPTY_BODY) - 1, out_memory, bytes, offsets);
+        }
+    }
     PosFeatParams F;
     F.p_off = P.prov.code_off;
     F.p_len = P.prov.code_len;
@@ -305,6 +330,11 @@ int hm_positions_geojson(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_
     return HM_OK;
 }
 
+int hm_positions_geojson(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t out_memory, const uint8_t **bytes,
+                         const int64_t **offsets, int64_t *n, const hm_position_rec **recs) {
+    return gj_positions(ctx, buckets, out_memory, bytes, offsets, n, recs, nullptr, "hm_positions_geojson");
+}
+
 int hm_selftest_position_features(const hm_position_doc_cfg *cfg, const hm_position_rec *recs, int64_t n, uint8_t *bytes,
                                   int64_t cap, int64_t *offsets) {
     if (!cfg || n < 0 || !bytes || !offsets || (n > 0 && !recs) || cap < (int64_t)sizeof(GJ_EMPTY_BODY) - 1) return HM_E_INVALID;
@@ -339,7 +369,7 @@ int hm_selftest_position_features(const hm_position_doc_cfg *cfg, const hm_posit
 int hm_geojson_info(const hm_ctx *ctx, int64_t *v, int32_t n) {
     if (!ctx || !v || n < 0) return HM_E_INVALID;
     const hm_ctx::GeoJson &G = ctx->gj;
-    const int64_t w[4] = {(int64_t)G.us[0], (int64_t)G.us[1], (int64_t)G.us[2], G.last_bytes};
-    for (int i = 0; i < n && i < 4; i++) v[i] = w[i];
+    const int64_t w[6] = {(int64_t)G.us[0], (int64_t)G.us[1], (int64_t)G.us[2], G.last_bytes, G.candidates, (int64_t)G.view_us};
+    for (int i = 0; i < n && i < 6; i++) v[i] = w[i];
     return HM_OK;
 }

@@ -187,6 +187,12 @@ struct hm_ctx {
         bool ready = false;
         double us[3] = {0, 0, 0};   // the last call's sizes kernel, write kernel, first to last event
         int64_t last_bytes = 0;     // the last call's body length
+        // the viewport calls (api_view.h, k_view.h): the kept tile records, the filter kernel's events and time, the
+        // candidates it saw
+        DevBuf vrecs;
+        hipEvent_t vev[2] = {};
+        double view_us = 0;
+        int64_t candidates = 0;
     } gj;
     DevBuf keys;                     // k_ingest's event key per row (kernels.h ekey)
     // k_ingest's fused binning (large direct-path batches): the bins' cursors (RP_BINS + 1 u32: the last stays 0, so
@@ -311,11 +317,13 @@ static void positions_free(hm_ctx *ctx) {
 static void geojson_free(hm_ctx *ctx) {
     hm_ctx::GeoJson &G = ctx->gj;
     for (DevBuf *b : {&G.in, &G.verts, &G.vn, &G.sizes, &G.off, &G.btot, &G.boff, &G.bytes, &G.words, &G.precs, &G.params,
-                      &G.bset, &G.blist})
+                      &G.bset, &G.blist, &G.vrecs})
         if (b->p) (void)hipFree(b->p);
     for (void *p : {G.h_bytes, G.h_off, G.h_recs})
         if (p) (void)hipHostFree(p);
     for (auto &e : G.ev)
+        if (e) (void)hipEventDestroy(e);
+    for (auto &e : G.vev)
         if (e) (void)hipEventDestroy(e);
 }
 

@@ -14,8 +14,9 @@
 //   k_rollup.h      read side: one window's tiles rolled up to a coarser resolution (k_rollup, k_rollup_emit)
 //   k_positions.h   the latest position per (provider, vehicleId) across batches (k_pos_*)
 //   k_geojson.h     read side: the response bodies as GeoJSON (geojson_docs.h, float_repr.h: k_gj_*)
+//   k_view.h        read side: a map viewport applied to cells, roll-up records and positions (k_cells_in_view, k_view_tiles)
 //   host_ctx.h      the context, allocation, per-window tables, launchers;  host_batch.h: the batch phases
-//   api_*.h         the C ABI of include/mobheat.h (batch, UDF/read side, stage API, checkpoint, sink, JSON, window reads, positions, GeoJSON, self-tests)
+//   api_*.h         the C ABI of include/mobheat.h (batch, UDF/read side, stage API, checkpoint, sink, JSON, window reads, positions, GeoJSON, viewport, self-tests)
 //
 // Pipeline per batch (one HIP stream per context; every arithmetic step runs on the GPU):
 //   k_ingest      filter (heatmap_stream.py:96-104) + H3 latLngToCell UDF (:65-75,105) + tumbling window (:115) +
@@ -88,6 +89,7 @@ static hipError_t upload_tables() {
 #include "k_rollup.h"
 #include "k_positions.h"
 #include "k_geojson.h"
+#include "k_view.h"
 #include "host_ctx.h"
 #include "host_batch.h"
 #include "host_pipe.h"
@@ -103,6 +105,7 @@ extern "C" {
 #include "api_read.h"
 #include "api_positions.h"
 #include "api_geojson.h"
+#include "api_view.h"
 #include "api_selftest.h"
 
 }  // extern "C"

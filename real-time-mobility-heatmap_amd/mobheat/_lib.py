@@ -100,6 +100,10 @@ class HmGeojsonCfg(ctypes.Structure):
                 ("end_len", c_i32)]
 
 
+class HmView(ctypes.Structure):
+    _fields_ = [("west", c_dbl), ("south", c_dbl), ("east", c_dbl), ("north", c_dbl)]
+
+
 # hm_state_rec (64 B): one live (cellId, windowStart) key of the tile state
 STATE_REC_DTYPE = np.dtype([("cell", "<u8"), ("window_start_us", "<i8"), ("count", "<i8"), ("n_speed", "<i8"),
                             ("sum_speed", "<f8"), ("sum_lat", "<f8"), ("sum_lon", "<f8"), ("reserved", "<i8")])
@@ -178,6 +182,12 @@ SIGNATURES = {
     "hm_positions_geojson": (c_i32, [c_vp, _P(HmPositionDocCfg), c_i32, _P(c_vp), _P(c_vp), _P(c_i64), _P(c_vp)]),
     "hm_selftest_position_features": (c_i32, [_P(HmPositionDocCfg), c_vp, c_i64, c_vp, c_i64, c_vp]),
     "hm_geojson_info": (c_i32, [c_vp, c_vp, c_i32]),
+    "hm_cells_in_view": (c_i32, [c_vp, c_i64, c_i32, c_i32, _P(HmView), c_vp]),
+    "hm_selftest_cells_in_view": (c_i32, [c_vp, c_i64, _P(HmView), c_vp]),
+    "hm_window_geojson_view": (c_i32, [c_vp, c_i64, c_i32, _P(HmGeojsonCfg), c_i32, _P(c_vp), _P(c_vp), _P(c_i64), _P(c_vp),
+                                       _P(HmView)]),
+    "hm_positions_geojson_view": (c_i32, [c_vp, _P(HmPositionDocCfg), c_i32, _P(c_vp), _P(c_vp), _P(c_i64), _P(c_vp),
+                                          _P(HmView)]),
     "hm_selftest_float_repr_host": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "hm_selftest_float_repr_device": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32]),
     "hm_abi_version": (c_i32, []),
@@ -558,3 +568,21 @@ def position_features_selftest(recs, providers, vehicles, bucket_ids, bucket_off
     check(lib.hm_selftest_position_features(ctypes.byref(cfg), ptr(recs) if recs.size else None, recs.size, ptr(buf), cap,
                                             ptr(offs)), None, "hm_selftest_position_features")
     return buf[:geojson_body_len(offs)].copy(), offs
+
+
+# ---- the read side for a map viewport (csrc/k_view.h) ----
+def view_struct(view):
+    """hm_view of (west, south, east, north) in degrees; validity is the library's to judge (HM_E_INVALID)."""
+    w, s, e, n = (float(x) for x in view)
+    return HmView(west=w, south=s, east=e, north=n)
+
+
+def cells_in_view_selftest(cells, view):
+    """Host execution of the device's view test (no GPU): uint8[n], 1 where the cell's boundary box meets the view."""
+    lib = load()
+    cells = np.ascontiguousarray(cells, dtype=np.uint64)
+    keep = np.zeros(cells.size, np.uint8)
+    v = view_struct(view)
+    check(lib.hm_selftest_cells_in_view(ptr(cells) if cells.size else None, cells.size, ctypes.byref(v),
+                                        ptr(keep) if cells.size else None), None, "hm_selftest_cells_in_view")
+    return keep

@@ -305,12 +305,14 @@ class HeatmapEngine:
         raw = np.ctypeslib.as_array(ctypes.cast(pb, ctypes.POINTER(ctypes.c_uint8)), shape=(_lib.geojson_body_len(offs),))
         return raw.tobytes() if copy else memoryview(raw)
 
-    def window_geojson(self, window_start_us=None, res=None, tz=None, copy=True, with_records=False):
+    def window_geojson(self, window_start_us=None, res=None, tz=None, copy=True, with_records=False, *, view=None):
         """The body of /api/tiles/latest for one live window (None: the newest) at H3 resolution res <= h3_res (None:
         h3_res): json.dumps(readside.tiles_latest_collection(...), separators=(",", ":")) as bytes, rolled up and
         encoded on the GPU in one call.  windowStart / windowEnd are formatted as readside.tile_docs_from_engine formats
         them (stream._spark_datetime, or zone tz's wall time).  copy=False: a memoryview of the library's pinned buffer,
-        valid until the next call on this engine.  with_records: (body, records in feature order, offsets) instead."""
+        valid until the next call on this engine.  with_records: (body, records in feature order, offsets) instead.
+        view=(west, south, east, north) in degrees: only the tiles whose boundary box meets the view, filtered on the GPU
+        between the roll-up and the encoder (hm_window_geojson_view; west > east crosses the antimeridian)."""
         import datetime as _dt
 
         from .stream import _spark_datetime
@@ -327,9 +329,16 @@ class HeatmapEngine:
         window_start_us = int(window_start_us)
         cfg, keep = _lib.geojson_cfg(when(window_start_us), when(window_start_us + self.tile_us))
         pb, po, pr, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
-        check(self._lib.hm_window_geojson(self._ctx, window_start_us, res, ctypes.byref(cfg), HM_MEM_HOST, ctypes.byref(pb),
-                                          ctypes.byref(po), ctypes.byref(n), ctypes.byref(pr) if with_records else None),
-              self._ctx, "hm_window_geojson")
+        if view is None:
+            check(self._lib.hm_window_geojson(self._ctx, window_start_us, res, ctypes.byref(cfg), HM_MEM_HOST, ctypes.byref(pb),
+                                              ctypes.byref(po), ctypes.byref(n), ctypes.byref(pr) if with_records else None),
+                  self._ctx, "hm_window_geojson")
+        else:
+            v = _lib.view_struct(view)
+            check(self._lib.hm_window_geojson_view(self._ctx, window_start_us, res, ctypes.byref(cfg), HM_MEM_HOST,
+                                                   ctypes.byref(pb), ctypes.byref(po), ctypes.byref(n),
+                                                   ctypes.byref(pr) if with_records else None, ctypes.byref(v)),
+                  self._ctx, "hm_window_geojson_view")
         body = self._geojson_body(pb, po, n.value, copy)
         if not with_records:
             return body
@@ -368,15 +377,23 @@ class HeatmapEngine:
             check(self._lib.hm_positions_buckets(self._ctx, ptr(ids), ids.size, ctypes.byref(n)), self._ctx, "hm_positions_buckets")
         return ids
 
-    def positions_geojson(self, tz=None, copy=True, with_records=False):
+    def positions_geojson(self, tz=None, copy=True, with_records=False, *, view=None):
         """The body of /api/positions/latest: json.dumps(readside.positions_latest_from_engine(...), separators=(",", ":"))
         as bytes, encoded on the GPU from the positions state.  ts is the naive local datetime the sink writes, or zone
-        tz's wall time (readside.position_docs_from_engine's convention).  copy / with_records as window_geojson."""
+        tz's wall time (readside.position_docs_from_engine's convention).  copy / with_records as window_geojson.
+        view=(west, south, east, north): only the positions inside it (hm_positions_geojson_view)."""
         cfg, keep = _lib.bucket_cfg(self.positions_buckets(), tz)
         pb, po, pr, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
-        check(self._lib.hm_positions_geojson(self._ctx, ctypes.byref(cfg), HM_MEM_HOST, ctypes.byref(pb), ctypes.byref(po),
-                                             ctypes.byref(n), ctypes.byref(pr) if with_records else None),
-              self._ctx, "hm_positions_geojson")
+        if view is None:
+            check(self._lib.hm_positions_geojson(self._ctx, ctypes.byref(cfg), HM_MEM_HOST, ctypes.byref(pb), ctypes.byref(po),
+                                                 ctypes.byref(n), ctypes.byref(pr) if with_records else None),
+                  self._ctx, "hm_positions_geojson")
+        else:
+            v = _lib.view_struct(view)
+            check(self._lib.hm_positions_geojson_view(self._ctx, ctypes.byref(cfg), HM_MEM_HOST, ctypes.byref(pb),
+                                                      ctypes.byref(po), ctypes.byref(n),
+                                                      ctypes.byref(pr) if with_records else None, ctypes.byref(v)),
+                  self._ctx, "hm_positions_geojson_view")
         body = self._geojson_body(pb, po, n.value, copy)
         if not with_records:
             return body
@@ -388,9 +405,10 @@ class HeatmapEngine:
         return body, recs, offs
 
     def geojson_info(self):
-        v = (ctypes.c_int64 * 4)()
-        check(self._lib.hm_geojson_info(self._ctx, v, 4), self._ctx, "hm_geojson_info")
-        return {"sizes_kernel_us": v[0], "write_kernel_us": v[1], "device_us": v[2], "body_bytes": v[3]}
+        v = (ctypes.c_int64 * 6)()
+        check(self._lib.hm_geojson_info(self._ctx, v, 6), self._ctx, "hm_geojson_info")
+        return {"sizes_kernel_us": v[0], "write_kernel_us": v[1], "device_us": v[2], "body_bytes": v[3],
+                "candidates": v[4], "view_kernel_us": v[5]}
 
     def _export_buffer(self, n, reuse, raw_out=None):
         """n state records of host memory: a fresh array, or (reuse) a view of the engine's page-locked export buffer --

@@ -27,6 +27,105 @@ def cells_to_boundary(cells, device=0):
     return lat, lng, nv
 
 
+# ---- a map viewport: (west, south, east, north) in degrees (include/mobheat.h hm_view) ----
+def view_valid(view):
+    """All four finite, -90 <= south <= north <= 90, -180 <= west, east <= 180."""
+    w, s, e, n = (float(x) for x in view)
+    return -90.0 <= s <= n <= 90.0 and -180.0 <= w <= 180.0 and -180.0 <= e <= 180.0
+
+
+def view_from_bbox(text):
+    """The view of a query string's bbox=west,south,east,north (Leaflet's getBounds().toBBoxString()): a tuple of four
+    floats.  ValueError for anything but four numbers that form a valid view (west > east is valid: the view crosses
+    the antimeridian)."""
+    parts = str(text).split(",")
+    if len(parts) != 4:
+        raise ValueError(f"bbox {text!r}: four comma-separated numbers expected (west,south,east,north)")
+    try:
+        view = tuple(float(p) for p in parts)
+    except ValueError:
+        raise ValueError(f"bbox {text!r}: not a number") from None
+    if not view_valid(view):
+        raise ValueError(f"bbox {text!r}: finite, -90 <= south <= north <= 90 and -180 <= west, east <= 180 expected")
+    return view
+
+
+def _view_lngs(view):
+    w, _, e, _ = view
+    return [(w, e)] if w <= e else [(w, 180.0), (-180.0, e)]
+
+
+def point_in_view(lat, lon, view):
+    """south <= lat <= north and lon in the view's longitudes (closed; plain float comparisons)."""
+    _, s, _, n = view
+    return bool(s <= lat <= n and any(a <= lon <= b for a, b in _view_lngs(view)))
+
+
+def ring_in_view(ring, view, pole=None):
+    """Does the latitude-longitude box of a GeoJSON ring [[lng, lat], ...] meet the view?  The ring's longitudes are
+    [min, max], or -- when they span more than 180 degrees, a ring across the antimeridian -- [min of the positive, 180]
+    and [-180, max of the others].  pole "north" / "south": the ring is that of the cell containing the pole (every
+    longitude, latitudes up to the pole).  An empty ring is never in view.  The comparison form of csrc/k_view.h."""
+    if not ring:
+        return False
+    lngs, lats = [float(p[0]) for p in ring], [float(p[1]) for p in ring]
+    la0, la1, lo0, lo1 = min(lats), max(lats), min(lngs), max(lngs)
+    if pole == "north":
+        la1 = 90.0
+    elif pole == "south":
+        la0 = -90.0
+    elif pole is not None:
+        raise ValueError("pole: None, 'north' or 'south'")
+    _, s, _, n = view
+    if not (la0 <= n and s <= la1):
+        return False
+    if pole is not None:
+        mine = [(-180.0, 180.0)]
+    elif lo1 - lo0 > 180.0:
+        mine = [(min(x for x in lngs if x > 0.0), 180.0), (-180.0, max(x for x in lngs if not x > 0.0))]
+    else:
+        mine = [(lo0, lo1)]
+    return any(a <= d and c <= b for a, b in mine for c, d in _view_lngs(view))
+
+
+def pole_cells(res):
+    """(north, south): the two cells of resolution res that contain a pole, latLngToCell(+-90, 0, res) (host execution)."""
+    c = _lib.latlng_to_cell_host_selftest(np.array([90.0, -90.0]), np.array([0.0, 0.0]), int(res))
+    return int(c[0]), int(c[1])
+
+
+def cells_in_view(cells, view, device=0):
+    """Which cells' boundary boxes meet the view, on the GPU (hm_cells_in_view): bool[n].  ValueError for an invalid view."""
+    import ctypes
+    if not view_valid(view):
+        raise ValueError(f"invalid view {tuple(view)!r}")
+    lib = _lib.load()
+    cells = np.ascontiguousarray(cells, dtype=np.uint64)
+    keep = np.zeros(cells.size, np.uint8)
+    if cells.size:
+        v = _lib.view_struct(view)
+        check(lib.hm_cells_in_view(ptr(cells), cells.size, HM_MEM_HOST, int(device), ctypes.byref(v), ptr(keep)), None,
+              "hm_cells_in_view")
+    return keep.astype(bool)
+
+
+def _tile_features_in_view(collection, view):
+    """the collection's features whose ring meets the view (the pure-Python filter)"""
+    if not view_valid(view):
+        raise ValueError(f"invalid view {tuple(view)!r}")
+    poles = {}
+    kept = []
+    for f in collection["features"]:
+        cell = _cell_int(f["properties"]["cellId"])
+        res = (cell >> 52) & 0xf
+        if res not in poles:
+            poles[res] = pole_cells(res)
+        pole = "north" if cell == poles[res][0] else "south" if cell == poles[res][1] else None
+        if ring_in_view(f["geometry"]["coordinates"][0], view, pole):
+            kept.append(f)
+    return {"type": "FeatureCollection", "features": kept}
+
+
 def _cell_int(cell_id):
     return int(cell_id, 16) if isinstance(cell_id, str) else int(cell_id)
 
@@ -87,12 +186,14 @@ def tile_docs_from_engine(engine, res=None, city="boston", tz=None, window_start
     return docs
 
 
-def tiles_latest_from_engine(engine, res=None, city="boston", tz=None):
+def tiles_latest_from_engine(engine, res=None, city="boston", tz=None, view=None):
     """The FeatureCollection api_tiles_latest returns (reference app.py:45-69) for the newest window the engine's
     state still holds, at H3 resolution res <= the engine's (None: the engine's own): the window's tiles rolled up on
     the GPU (hm_window_rollup), their boundaries from one more launch (tiles_latest_collection).  "Latest" is the
-    newest window the watermark has not evicted; the reference's Mongo keeps windows until their TTL."""
-    return tiles_latest_collection(tile_docs_from_engine(engine, res, city, tz), engine.device)
+    newest window the watermark has not evicted; the reference's Mongo keeps windows until their TTL.
+    view=(west, south, east, north): only the tiles in view, filtered here in Python (ring_in_view)."""
+    fc = tiles_latest_collection(tile_docs_from_engine(engine, res, city, tz), engine.device)
+    return fc if view is None else _tile_features_in_view(fc, view)
 
 
 def positions_latest_collection(docs):
@@ -128,20 +229,29 @@ def position_docs_from_engine(engine, tz=None):
     return docs
 
 
-def positions_latest_from_engine(engine, tz=None):
+def positions_latest_from_engine(engine, tz=None, view=None):
     """The FeatureCollection api_positions_latest returns (reference app.py:71-88), from the engine's positions state
-    (HeatmapEngine.update_positions after each batch) -- no MongoDB in between."""
-    return positions_latest_collection(position_docs_from_engine(engine, tz))
+    (HeatmapEngine.update_positions after each batch) -- no MongoDB in between.  view=(west, south, east, north): only
+    the positions in view, filtered here in Python (point_in_view)."""
+    fc = positions_latest_collection(position_docs_from_engine(engine, tz))
+    if view is None:
+        return fc
+    if not view_valid(view):
+        raise ValueError(f"invalid view {tuple(view)!r}")
+    kept = [f for f in fc["features"] if point_in_view(f["geometry"]["coordinates"][1], f["geometry"]["coordinates"][0], view)]
+    return {"type": "FeatureCollection", "features": kept}
 
 
-def tiles_latest_body(engine, res=None, tz=None):
+def tiles_latest_body(engine, res=None, tz=None, view=None):
     """The response body of api_tiles_latest as bytes: json.dumps(tiles_latest_from_engine(engine, res, tz=tz),
     separators=(",", ":")), rolled up and encoded on the GPU in one call (HeatmapEngine.window_geojson).  The dict-building
-    functions above stay as the comparison form, as stream.tile_ops is for the sink."""
-    return engine.window_geojson(None, res, tz)
+    functions above stay as the comparison form, as stream.tile_ops is for the sink.  view: the tiles in view only,
+    filtered on the GPU."""
+    return engine.window_geojson(None, res, tz, view=view)
 
 
-def positions_latest_body(engine, tz=None):
+def positions_latest_body(engine, tz=None, view=None):
     """The response body of api_positions_latest as bytes: json.dumps(positions_latest_from_engine(engine, tz),
-    separators=(",", ":")), encoded on the GPU from the positions state (HeatmapEngine.positions_geojson)."""
-    return engine.positions_geojson(tz)
+    separators=(",", ":")), encoded on the GPU from the positions state (HeatmapEngine.positions_geojson).  view: the
+    positions in view only, filtered on the GPU."""
+    return engine.positions_geojson(tz, view=view)
