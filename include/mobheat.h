@@ -629,7 +629,14 @@ int hm_selftest_float_repr_device(const double *x, int64_t n, uint8_t *text, int
  * wave-cooperative probe, 4 the bins' records read as segments, 8 at least one record of the batch probed its slot
  * through HBM (0: the batch merged nothing; a growth's rehash merge is not recorded).  Tests choose the variant with
  * MOBHEAT_TEST_MERGE_TAGS=<bytes> (at most that much LDS for resident tags; 0: none) and MOBHEAT_TEST_MERGE_COOP=0|1
- * (the probe of a resident-only merge), read at hm_create. */
+ * (the probe of a resident-only merge), read at hm_create.  [13]..[18] the regimes of a table-mode batch (0 on the
+ * other paths): [13] flushes of a full aggregation table before a workgroup's last one, summed over workgroups, [14]
+ * rows sent as partial records of their own because the table's probe bound was reached, [15] evicted aggregates sent
+ * so because their bucket was full, [16] bucket records sent so because the reducing table's probe bound was reached,
+ * [17] emissions of a full reducing table before a bucket's last one, summed over buckets, [18] the bucket capacity
+ * (records per sub-bucket) the batch ran with.  Tests reach them on small batches with MOBHEAT_TEST_AGG_GRID=<g> (the
+ * aggregation's row spans as if the device had g compute units) and MOBHEAT_TEST_AGG_CAP=<f> (the floor of the bucket
+ * capacity instead of 4096), read at hm_create. */
 int hm_last_counts(const hm_ctx *ctx, int64_t *c, int32_t n);
 /* Version of the persistent tile state: incremented when a batch starts merging into it (hm_process_batch,
  * hm_stage_merge, growth).  A call that failed without changing it left the state as it was (-1: ctx NULL). */

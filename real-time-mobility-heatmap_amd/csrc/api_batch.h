@@ -143,6 +143,12 @@ int hm_create(const hm_config *cfg, hm_ctx **out) {
     // cooperative probe of a resident merge, whatever the batch's share of existing keys (merge_sorted)
     if (const char *m = getenv("MOBHEAT_TEST_MERGE_TAGS")) ctx->test_merge_tags = std::max(0, atoi(m));
     if (const char *m = getenv("MOBHEAT_TEST_MERGE_COOP")) ctx->test_merge_coop = strcmp(m, "0") != 0;
+    // MOBHEAT_TEST_AGG_GRID (tests): k_agg's spans as if the device had that many CUs, so that with 1 a few thousand
+    // rows are many rounds of one workgroup; MOBHEAT_TEST_AGG_CAP (tests): the floor of the sub-bucket capacity instead
+    // of 4096 records, so that a small batch overflows its sub-buckets and the next one shows the capacity grow
+    // (phase_table)
+    if (const char *m = getenv("MOBHEAT_TEST_AGG_GRID")) ctx->test_agg_grid = std::max(0, atoi(m));
+    if (const char *m = getenv("MOBHEAT_TEST_AGG_CAP")) ctx->test_agg_cap = (unsigned)std::max(0, atoi(m));
     // the registry, its census and the batch statistics side by side (one reset, one readback after k_ingest)
     if (hipMalloc(&ctx->d_wreg, REG_BLOCK_BYTES) != hipSuccess || !(ctx->d_wcount = ctx->d_wreg + WREG_SLOTS + 1) ||
         !(ctx->d_st = (DevStats *)(ctx->d_wreg + 2 * (WREG_SLOTS + 1))) ||
@@ -311,6 +317,7 @@ int hm_last_counts(const hm_ctx *ctx, int64_t *c, int32_t n) {
     if (n > 10) c[10] = ctx->staged ? 0 : ctx->last_pipe_chunks;
     if (n > 11) c[11] = ctx->last_ring_direct;
     if (n > 12) c[12] = ctx->last_merge_variant;
+    for (int i = 13; i < n && i < 19; i++) c[i] = ctx->last_counts[3] ? ctx->table_regimes[i - 13] : 0;
     return HM_OK;
 }
 

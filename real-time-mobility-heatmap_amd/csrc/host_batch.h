@@ -207,8 +207,10 @@ static int phase_table(hm_ctx *ctx, const Inputs &I, int64_t n_agg, int64_t *n_p
     if ((rc = keys_complete(ctx, I))) return rc;
     if ((rc = ensure(ctx, ctx->partials, std::max<int64_t>(n_agg, 1) * sizeof(TilePartial)))) return rc;
     const int nsub = AG_BINS * AG_SUB;
+    const int64_t cap_floor = ctx->test_agg_cap ? ctx->test_agg_cap : 4096;   // (MOBHEAT_TEST_AGG_CAP)
     if (ctx->agg_cap == 0)   // first table batch: room for about a quarter of the rows evicted twice over
-        ctx->agg_cap = (unsigned)std::min<int64_t>(std::max<int64_t>(4096, n_agg / (2 * nsub)), int64_t(1) << 30);
+        ctx->agg_cap = (unsigned)std::min<int64_t>(std::max<int64_t>(cap_floor, n_agg / (2 * nsub)), int64_t(1) << 30);
+    const unsigned cap = ctx->agg_cap;
     if ((rc = ensure(ctx, ctx->agg_bucket, (size_t)nsub * ctx->agg_cap * sizeof(AggRec))) ||
         (rc = ensure(ctx, ctx->agg_cursor, (size_t)nsub * 8)))
         return rc;
@@ -216,7 +218,8 @@ static int phase_table(hm_ctx *ctx, const Inputs &I, int64_t n_agg, int64_t *n_p
     HIPCHK(ctx, hipMemsetAsync(ctx->d_cmap, 0, GMAP_SLOTS * sizeof(WinCount), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(&ctx->d_st->n_partials, 0, 8, ctx->stream));
     if (n > 0) {
-        const int64_t per = (n + ctx->n_cus - 1) / ctx->n_cus;
+        const int64_t cus = ctx->test_agg_grid ? ctx->test_agg_grid : ctx->n_cus;   // (MOBHEAT_TEST_AGG_GRID)
+        const int64_t per = (n + cus - 1) / cus;
         const int64_t span = std::max<int64_t>((per + AG_THREADS - 1) / AG_THREADS, 1) * AG_THREADS;
         const uint64_t ch = cell_hi_of(ctx->cfg.h3_res);
         hipLaunchKernelGGL(k_agg, dim3((unsigned)((n + span - 1) / span)), dim3(AG_THREADS), 0, ctx->stream,
@@ -235,10 +238,15 @@ static int phase_table(hm_ctx *ctx, const Inputs &I, int64_t n_agg, int64_t *n_p
     if (ctx->h_st->overflow) return set_err(ctx, HM_E_OVERFLOW, "more than %d windows in one batch", GMAP_SLOTS);
     *n_parts = (int64_t)ctx->h_st->n_partials;
     ctx->table_evicted = (int64_t)ctx->h_st->n_evicted;
+    const DevStats &ts = *ctx->h_st;
+    const int64_t regimes[6] = {(int64_t)ts.agg_flushes,  (int64_t)ts.agg_spill[AGG_SPILL_PROBE], (int64_t)ts.agg_spill[AGG_SPILL_CAP],
+                                (int64_t)ts.agg_spill[BIN_SPILL_PROBE], (int64_t)ts.bin_emits, (int64_t)cap};
+    std::copy(regimes, regimes + 6, ctx->table_regimes);
     // the next table batch's sub-bucket capacity: twice this batch's fullest one (shrinks slowly)
     unsigned long long mx = 0;
     for (unsigned long long c : ctx->h_agg_cursor) mx = std::max(mx, c);
-    const unsigned want = (unsigned)std::min<unsigned long long>(std::max<unsigned long long>(4096, 2 * mx), 1ull << 30);
+    const unsigned want =
+        (unsigned)std::min<unsigned long long>(std::max<unsigned long long>((unsigned long long)cap_floor, 2 * mx), 1ull << 30);
     if (want > ctx->agg_cap || want < ctx->agg_cap / 4) ctx->agg_cap = want;
     ctx->census_ready = true;
     return HM_OK;

@@ -128,6 +128,12 @@ struct hm_ctx {
     int64_t last_counts[6] = {0, 0, 0, 0, 0, 0};   // hm_last_counts [0, 6) ([6], [7]: n_allocs, n_frees)
     int64_t n_allocs = 0, n_frees = 0;             // device + pinned-host allocations / frees since create
     int64_t table_evicted = 0;                   // table mode: aggregates k_agg evicted into its buckets (last batch)
+    // hm_last_counts [13, 19): the last table batch's regimes (phase_table) -- k_agg's non-final flushes, the spills by
+    // cause (k_agg's probe bound, a full bucket, k_bin_reduce's probe bound), k_bin_reduce's non-final emissions, and
+    // the sub-bucket capacity the kernels ran with
+    int64_t table_regimes[6] = {0, 0, 0, 0, 0, 0};
+    int test_agg_grid = 0;          // MOBHEAT_TEST_AGG_GRID: k_agg's spans as if the device had this many CUs (tests; 0: unset)
+    unsigned test_agg_cap = 0;      // MOBHEAT_TEST_AGG_CAP: the floor of agg_cap instead of 4096 (tests; 0: unset)
     // hm_decode_json (row f1): the values on the device, the decoded columns, the string dictionaries
     struct Dict {
         DevBuf tab, slot_of, occ, slots, code_of_slot, clen, coff, cbytes, btot, boff;

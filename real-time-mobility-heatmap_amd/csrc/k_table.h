@@ -110,12 +110,14 @@ __device__ __forceinline__ TilePartial ag_partial(uint64_t k, unsigned long long
     p.slon = slo;
     return p;
 }
-__device__ __forceinline__ void ag_spill(uint64_t k, unsigned long long c, double ssp, double sla, double slo,
+// why an aggregate went out as a partial record of its own (DevStats::agg_spill's index)
+enum AggSpill { AGG_SPILL_PROBE = 0, AGG_SPILL_CAP = 1, BIN_SPILL_PROBE = 2 };
+__device__ __forceinline__ void ag_spill(AggSpill why, uint64_t k, unsigned long long c, double ssp, double sla, double slo,
                                          const unsigned long long *wreg, uint64_t cell_hi, TilePartial *out, DevStats *st,
                                          WinLds &WL, const CensusSink &census, bool &ok) {
     const TilePartial p = ag_partial(k, c, ssp, sla, slo, wreg, cell_hi);
     out[atomicAdd(&st->n_partials, 1ull)] = p;
-    atomicAdd(&st->agg_spill, 1ull);
+    atomicAdd(&st->agg_spill[why], 1ull);
     ok &= wl_add(WL, census, wenc_of(p.wstart), 1ull);
 }
 // k_agg's flush: the entries below the keep threshold go to their buckets; kept ones are re-inserted into the
@@ -194,7 +196,7 @@ __device__ void ag_flush(AgTable &T, bool final, AggRec *__restrict__ bucket, un
             r.pad = 0;
             bucket[(uint64_t)(bin * AG_SUB + xs) * cap + pos] = r;
         } else {
-            ag_spill(k, c, a, b, d, wreg, cell_hi, out, st, WL, census, ok);
+            ag_spill(AGG_SPILL_CAP, k, c, a, b, d, wreg, cell_hi, out, st, WL, census, ok);
         }
     }
     evicted = wave_sum(evicted);
@@ -249,6 +251,7 @@ __global__ __launch_bounds__(AG_THREADS) void k_agg(const uint64_t *__restrict__
     const int64_t b0 = (int64_t)blockIdx.x * span;
     const int64_t b1 = b0 + span < n ? b0 + span : n;
     FreshCount FC(fresh_ctr);
+    unsigned n_flushes = 0;   // (the same in every thread: one add per workgroup, at the end)
     // a row's columns, loaded one round ahead (the round's loads are in flight while the previous one aggregates).
     // (Measured on C3: keeping the validity byte raw and waiting for the first round before the loop -- so that no
     // round waits for the next round's loads -- made k_agg 0.3 ms slower, profiles/r2/ab1/: its rounds are not
@@ -271,11 +274,13 @@ __global__ __launch_bounds__(AG_THREADS) void k_agg(const uint64_t *__restrict__
         if (k) {
             const double sp = r.sv ? r.sp : 0.0, la = r.la, lo = r.lo;
             const unsigned long long c = 1ull | ((unsigned long long)r.sv << 32);
-            if (!ag_add(T, k, c, sp, la, lo, fresh)) ag_spill(k, c, sp, la, lo, wreg, cell_hi, out, st, WL, census, ok);
+            if (!ag_add(T, k, c, sp, la, lo, fresh))
+                ag_spill(AGG_SPILL_PROBE, k, c, sp, la, lo, wreg, cell_hi, out, st, WL, census, ok);
         }
         if (FC.round(fresh) > (unsigned)AG_FLUSH_AT) {
             ag_flush(T, false, bucket, cursor, cap, wreg, cell_hi, out, st, WL, census, ok);
             FC.occ = T.occ;
+            n_flushes++;
         }
     };
     Row nx = load(b0 + threadIdx.x);
@@ -286,6 +291,7 @@ __global__ __launch_bounds__(AG_THREADS) void k_agg(const uint64_t *__restrict__
     }
     ag_flush(T, true, bucket, cursor, cap, wreg, cell_hi, out, st, WL, census, ok);
     __syncthreads();
+    if (n_flushes && threadIdx.x == 0) atomicAdd(&st->agg_flushes, (unsigned long long)n_flushes);
     ok &= wl_flush(WL, census);
     if (__ballot(!ok) && lane_id() == 0) atomicAdd(&st->overflow, 1ull);
 }
@@ -358,6 +364,7 @@ __global__ __launch_bounds__(AG_THREADS) void k_bin_reduce(const AggRec *__restr
     bool ok = true;
     const unsigned long long total = sub_end[AG_SUB];
     FreshCount FC(fresh_ctr);
+    unsigned n_emits = 0;
     for (unsigned long long c0 = 0; c0 < total; c0 += AG_THREADS) {
         const unsigned long long j = c0 + threadIdx.x;
         bool fresh = false;
@@ -366,14 +373,16 @@ __global__ __launch_bounds__(AG_THREADS) void k_bin_reduce(const AggRec *__restr
             while (j >= sub_end[x + 1]) x++;
             const AggRec r = bucket[(uint64_t)(bin * AG_SUB + x) * cap + (j - sub_end[x])];
             if (!ag_add(T, r.key, r.cnt, r.ssp, r.slat, r.slon, fresh))
-                ag_spill(r.key, r.cnt, r.ssp, r.slat, r.slon, wreg, cell_hi, out, st, WL, census, ok);
+                ag_spill(BIN_SPILL_PROBE, r.key, r.cnt, r.ssp, r.slat, r.slon, wreg, cell_hi, out, st, WL, census, ok);
         }
         if (FC.round(fresh) > (unsigned)AG_FLUSH_AT) {
             ag_emit_all(T, wreg, cell_hi, out, st, WL, census, ok);
             FC.occ = 0;
+            n_emits++;
         }
     }
     ag_emit_all(T, wreg, cell_hi, out, st, WL, census, ok);
+    if (n_emits && threadIdx.x == 0) atomicAdd(&st->bin_emits, (unsigned long long)n_emits);
     ok &= wl_flush(WL, census);
     if (__ballot(!ok) && lane_id() == 0) atomicAdd(&st->overflow, 1ull);
 }

@@ -198,8 +198,13 @@ struct DevStats {
     unsigned long long dedup_retry; // k_ingest: a vkey probe hit its bound; rerun k_dedup_max on a larger table
     unsigned long long n_gaps;      // partial slots holding no record (gaps)
     unsigned long long win_overflow; // k_ingest: rows of windows beyond the batch's window registry (WREG_SLOTS)
-    unsigned long long agg_spill;   // table mode: aggregates that did not fit a bucket (sent as partial records)
+    // table mode: aggregates sent as partial records instead of through a bucket, by cause (AggSpill indexes them;
+    // hm_last_counts [14..16]) -- k_agg's row found no slot within AG_PROBES, ag_flush's bucket was full, k_bin_reduce's
+    // record found no slot
+    unsigned long long agg_spill[3];
     unsigned long long n_evicted;   // table mode: aggregates k_agg evicted into the buckets
+    unsigned long long agg_flushes; // table mode: k_agg's flushes before its last one, over all workgroups ([13])
+    unsigned long long bin_emits;   // table mode: k_bin_reduce's emissions of a full table before its last one ([17])
     unsigned long long sample_max_run;   // k_sample_heavy: occurrences of the most frequent key in a key sample
     unsigned long long bin_overflow;     // k_ingest<true>: rows whose bin slab was full (the batch re-partitions)
     unsigned long long vkey_max1;        // k_ingest: max vkey + 1 of its deduplicated rows (capped at 2^62; sizes the
