@@ -33,6 +33,7 @@
  *   hm_window_geojson / hm_positions_geojson -- the two endpoints' response bodies (app.py:45-88) as GeoJSON encoded on
  *                                   the GPU, byte for byte json.dumps of the collections the reference builds in Python.
  *   hm_window_geojson_view / hm_positions_geojson_view / hm_cells_in_view -- the same for a client's map viewport.
+ *   hm_window_raster             -- a live window's counts per pixel of a grid, for z/x/y raster tiles of the heatmap.
  */
 #ifndef MOBHEAT_H
 #define MOBHEAT_H
@@ -608,6 +609,37 @@ int hm_window_geojson_view(hm_ctx *ctx, int64_t window_start_us, int32_t res, co
 /* hm_positions_geojson of the positions in view (*n = the kept count); its errors, and HM_E_INVALID for an invalid view */
 int hm_positions_geojson_view(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t out_memory, const uint8_t **bytes,
                               const int64_t **offsets, int64_t *n, const hm_position_rec **recs, const hm_view *view);
+
+/* ---- a live window as a raster, for web-map z/x/y tiles (the reference's UI loads its base layer as such tiles,
+ * app.py:122, and colours hexagons in seven count classes, colorByCount, app.py:135-142) ----
+ * The grid is separable: rows latitudes lat[rows] and cols longitudes lon[cols], degrees, host memory; pixel (r, c) has
+ * the centre (lat[r], lon[c]) and the index r * cols + c.  The caller projects (mobheat/readside.py tile_grid: the pixel
+ * centres of slippy-map tile z/x/y); the library never does.  A pixel's value is the count of the record hm_window_rollup
+ * gives for the cell latLngToCell(lat[r], lon[c], res) -- the hexagon that contains the pixel's centre, the one
+ * hm_window_geojson draws there; exact, no tolerance.  A NaN or out-of-range coordinate has no cell: count 0.
+ *   counts   uint32 per pixel: the record's count saturated at 0xFFFFFFFF; 0 where the window has no tile at that cell
+ *   classes  uint8 per pixel (only with n_thresholds > 0 and classes non-NULL; classes may be NULL otherwise): the number
+ *            of thresholds t with count > t -- strict, on the unsaturated 64-bit count.  thresholds: host memory, 0..15 of
+ *            them, each >= 0, strictly ascending.  (0, 2, 5, 10, 20, 50) gives colorByCount's classes, 0 = no tile.
+ * Outputs as hm_window_rollup's: library-owned, device or pinned host memory per out_memory, valid until the next call on
+ * the context; buffers of the raster's own.  Reads the state only (hm_state_version, the next batch and a checkpoint
+ * export in progress are unaffected); a repeated call of the same shape allocates nothing.  A window that is not live:
+ * an all-zero grid.  rows * cols == 0: HM_OK, nothing written (*counts NULL).  HM_E_INVALID, the message naming the limit:
+ * rows or cols < 0 or > 16384, rows * cols > 2^26, bad thresholds, res outside 0..h3_res.  Between stage calls: HM_E_STATE.
+ * On a shard context the counts cover the keys that rank owns: the caller adds the ranks' grids (counts add exactly up to
+ * the saturation) and classifies the sum; n_thresholds > 0 there is HM_E_INVALID. */
+int hm_window_raster(hm_ctx *ctx, int64_t window_start_us, int32_t res, const double *lat, int32_t rows, const double *lon,
+                     int32_t cols, const int64_t *thresholds, int32_t n_thresholds, int32_t out_memory,
+                     const uint32_t **counts, const uint8_t **classes);
+/* Host execution of the same per-pixel code on caller records (no GPU; records of equal cell add up; window_start_us and
+ * the sums are not read).  res 0..15; the grid's and the thresholds' limits as above. */
+int hm_selftest_window_raster(const hm_state_rec *recs, int64_t n, int32_t res, const double *lat, int32_t rows,
+                              const double *lon, int32_t cols, const int64_t *thresholds, int32_t n_thresholds,
+                              uint32_t *counts, uint8_t *classes);
+/* up to n of, for the last hm_window_raster call on the context: [0] its pixels, [1] of those, the pixels the fast
+ * latLngToCell handed to the exact path, [2] the records in the roll-up's table (0: the window was not live), [3] its two
+ * kernels, microseconds (HIP events). */
+int hm_raster_info(const hm_ctx *ctx, int64_t *v, int32_t n);
 
 /* json.dumps(x) of n doubles -- CPython's float.__repr__, NaN / Infinity / -Infinity for the non-finite -- as the GeoJSON
  * encoders write them (csrc/float_repr.h), executed on the host and on GPU `device` (test entry points): value i's

@@ -22,12 +22,16 @@ int hm_live_windows(hm_ctx *ctx, int64_t *window_start_us, int64_t *keys, int64_
 // of its own (ru_tab, ru_out, h_ru), so that a checkpoint dump waiting in parts_regrow stays as it is.
 // Leaves *m_out records of window window_start_us at res in ctx->ru_out (0: the window is not live); `who` names the
 // entry point in the errors (hm_window_rollup, and hm_window_geojson, which encodes the records where they are).
-static int rollup_on_device(hm_ctx *ctx, int64_t window_start_us, int32_t res, const char *who, int64_t *m_out) {
+// nslots_out (optional): the slots of the parent table in ctx->ru_tab, which stays probe-able until the next roll-up
+// (hm_window_raster looks the pixels' cells up there); 0 when the window is not live.
+static int rollup_on_device(hm_ctx *ctx, int64_t window_start_us, int32_t res, const char *who, int64_t *m_out,
+                            int64_t *nslots_out = nullptr) {
     static_assert(sizeof(hm_state_rec) == sizeof(GrowRec), "hm_state_rec mirrors GrowRec");
     if (res < 0 || res > ctx->cfg.h3_res)
         return set_err(ctx, HM_E_INVALID, "roll-up resolution %d outside 0..%d", res, ctx->cfg.h3_res);
     if (ctx->stage != 0) return set_err(ctx, HM_E_STATE, "%s between stage calls", who);
     *m_out = 0;
+    if (nslots_out) *nslots_out = 0;
     const hm_ctx::Gen *gen = nullptr;
     for (const auto &g : ctx->gens)
         if (g.wenc == wenc_of(window_start_us) && g.keys > 0) gen = &g;
@@ -58,6 +62,7 @@ static int rollup_on_device(hm_ctx *ctx, int64_t window_start_us, int32_t res, c
     if ((int64_t)got[0] > bound)
         return set_err(ctx, HM_E_STATE, "roll-up found %llu parents, at most %lld expected", got[0], (long long)bound);
     *m_out = (int64_t)got[0];
+    if (nslots_out) *nslots_out = nslots;
     return HM_OK;
 }
 

@@ -200,6 +200,16 @@ struct hm_ctx {
         double view_us = 0;
         int64_t candidates = 0;
     } gj;
+    // hm_window_raster (api_raster.h, k_raster.h): the grid's coordinates, the two outputs, the exception list and its
+    // counter -- buffers of its own (not ru_out, h_ru or the GeoJSON ones).  Nothing here is allocated before the first call.
+    struct Raster {
+        DevBuf lat, lon, counts, classes, slow, words;
+        void *h_counts = nullptr, *h_classes = nullptr;   // pinned host copies
+        size_t h_counts_cap = 0, h_classes_cap = 0;
+        hipEvent_t ev[2] = {};   // before k_raster, after k_raster_exact
+        bool ready = false;
+        int64_t info[4] = {0, 0, 0, 0};   // hm_raster_info: pixels, exact-path pixels, records in the table, kernel us
+    } raster;
     DevBuf keys;                     // k_ingest's event key per row (kernels.h ekey)
     // k_ingest's fused binning (large direct-path batches): the bins' cursors (RP_BINS + 1 u32: the last stays 0, so
     // that their exclusive scan ends with the total) and the slab capacity; the slabs are parts_sorted
@@ -330,6 +340,17 @@ static void geojson_free(hm_ctx *ctx) {
     for (auto &e : G.ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : G.vev)
+        if (e) (void)hipEventDestroy(e);
+}
+
+// hm_destroy's part for the raster
+static void raster_free(hm_ctx *ctx) {
+    hm_ctx::Raster &R = ctx->raster;
+    for (DevBuf *b : {&R.lat, &R.lon, &R.counts, &R.classes, &R.slow, &R.words})
+        if (b->p) (void)hipFree(b->p);
+    for (void *p : {R.h_counts, R.h_classes})
+        if (p) (void)hipHostFree(p);
+    for (auto &e : R.ev)
         if (e) (void)hipEventDestroy(e);
 }
 

@@ -188,6 +188,9 @@ SIGNATURES = {
                                        _P(HmView)]),
     "hm_positions_geojson_view": (c_i32, [c_vp, _P(HmPositionDocCfg), c_i32, _P(c_vp), _P(c_vp), _P(c_i64), _P(c_vp),
                                           _P(HmView)]),
+    "hm_window_raster": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, _P(c_vp), _P(c_vp)]),
+    "hm_selftest_window_raster": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "hm_raster_info": (c_i32, [c_vp, c_vp, c_i32]),
     "hm_selftest_float_repr_host": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "hm_selftest_float_repr_device": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32]),
     "hm_abi_version": (c_i32, []),
@@ -586,3 +589,28 @@ def cells_in_view_selftest(cells, view):
     check(lib.hm_selftest_cells_in_view(ptr(cells) if cells.size else None, cells.size, ctypes.byref(v),
                                         ptr(keep) if cells.size else None), None, "hm_selftest_cells_in_view")
     return keep
+
+
+# ---- a window as a raster (csrc/k_raster.h) ----
+def raster_args(lat, lon, thresholds):
+    """(lat float64[rows], lon float64[cols], thresholds int64[k] or None) as contiguous arrays; the limits are the
+    library's to judge (HM_E_INVALID)."""
+    lat = np.ascontiguousarray(lat, dtype=np.float64).reshape(-1)
+    lon = np.ascontiguousarray(lon, dtype=np.float64).reshape(-1)
+    thr = None if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.int64).reshape(-1)
+    return lat, lon, thr
+
+
+def window_raster_selftest(recs, res, lat, lon, thresholds=None):
+    """Host execution of the raster's per-pixel code (no GPU) on STATE_REC_DTYPE records: counts uint32[rows, cols], or
+    (counts, classes uint8[rows, cols]) when thresholds are given."""
+    lib = load()
+    recs = np.ascontiguousarray(recs, dtype=STATE_REC_DTYPE)
+    lat, lon, thr = raster_args(lat, lon, thresholds)
+    counts = np.zeros((lat.size, lon.size), np.uint32)
+    classes = None if thr is None else np.zeros((lat.size, lon.size), np.uint8)
+    check(lib.hm_selftest_window_raster(ptr(recs) if recs.size else None, recs.size, int(res), ptr(lat), lat.size, ptr(lon),
+                                        lon.size, None if thr is None else ptr(thr), 0 if thr is None else thr.size,
+                                        ptr(counts), None if classes is None else ptr(classes)), None,
+          "hm_selftest_window_raster")
+    return counts if thr is None else (counts, classes)

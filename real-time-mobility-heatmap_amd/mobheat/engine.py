@@ -298,6 +298,42 @@ class HeatmapEngine:
         return TileRows(cell=r["cell"].astype(np.uint64), window_start_us=ws, window_end_us=ws + self.tile_us, count=cnt,
                         avg_speed=avg_speed, speed_null=~has, avg_lon=r["sum_lon"] / cnt, avg_lat=r["sum_lat"] / cnt)
 
+    # ---- one window as a raster over a separable pixel grid (hm_window_raster) ----
+    def window_raster(self, lat, lon, window_start_us=None, res=None, thresholds=None, copy=True):
+        """The counts of one live window (None: the newest) over the grid lat[rows] x lon[cols] (degrees; readside.tile_grid
+        gives a slippy-map tile's): counts uint32[rows, cols], the count of the tile at resolution res <= h3_res (None:
+        h3_res) whose hexagon contains the pixel's centre, saturated at 2^32 - 1, 0 where there is none -- rolled up and
+        looked up on the GPU in one call.  thresholds (ascending ints): (counts, classes uint8[rows, cols]) instead, a
+        pixel's class the number of thresholds its count exceeds.  A window that is not live, or no window at all: zeros.
+        copy=False: views of the library's pinned buffers, valid until the next call on this engine.  On a shard engine:
+        the keys this rank owns (add the ranks' grids; thresholds are refused there)."""
+        res = self.h3_res if res is None else int(res)
+        lat, lon, thr = _lib.raster_args(lat, lon, thresholds)
+        if window_start_us is None:
+            ws, _ = self.live_windows()
+            window_start_us = ws[-1] if ws.size else 0
+        pc, pk = ctypes.c_void_p(), ctypes.c_void_p()
+        check(self._lib.hm_window_raster(self._ctx, int(window_start_us), res, ptr(lat), lat.size, ptr(lon), lon.size,
+                                         None if thr is None else ptr(thr), 0 if thr is None else thr.size, HM_MEM_HOST,
+                                         ctypes.byref(pc), ctypes.byref(pk) if thr is not None else None),
+              self._ctx, "hm_window_raster")
+        shape, n = (lat.size, lon.size), lat.size * lon.size
+
+        def grid(p, ct, dt):
+            if n == 0 or not p:
+                return np.zeros(shape, dt)
+            a = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ct)), shape=(n,)).reshape(shape)
+            return a.copy() if copy else a
+        counts = grid(pc, ctypes.c_uint32, np.uint32)
+        if thr is None:
+            return counts
+        return counts, (grid(pk, ctypes.c_uint8, np.uint8) if thr.size else np.zeros(shape, np.uint8))
+
+    def raster_info(self):
+        v = (ctypes.c_int64 * 4)()
+        check(self._lib.hm_raster_info(self._ctx, v, 4), self._ctx, "hm_raster_info")
+        return {"pixels": v[0], "exact_pixels": v[1], "records": v[2], "kernel_us": v[3]}
+
     # ---- the read side's response bodies, GeoJSON-encoded on the GPU (hm_window_geojson / hm_positions_geojson) ----
     @staticmethod
     def _geojson_body(pb, po, n, copy):

@@ -255,3 +255,64 @@ def positions_latest_body(engine, tz=None, view=None):
     separators=(",", ":")), encoded on the GPU from the positions state (HeatmapEngine.positions_geojson).  view: the
     positions in view only, filtered on the GPU."""
     return engine.positions_geojson(tz, view=view)
+
+
+# ---- the newest window as web-map raster tiles (HeatmapEngine.window_raster, csrc/k_raster.h) ----
+# the reference page's colorByCount (app.py:135-142): class k = the number of thresholds a count exceeds; class 0 -- no
+# tile -- is its '#FFEDA0' made fully transparent, the six others its colours in ascending order at its fillOpacity 0.6
+COUNT_THRESHOLDS = (0, 2, 5, 10, 20, 50)
+COUNT_PALETTE = ((0xFF, 0xED, 0xA0, 0), (0xFE, 0xB2, 0x4C, 153), (0xFD, 0x8D, 0x3C, 153), (0xFC, 0x4E, 0x2A, 153),
+                 (0xE3, 0x1A, 0x1C, 153), (0xBD, 0x00, 0x26, 153), (0x80, 0x00, 0x26, 153))
+
+
+def tile_grid(z, x, y, size=256):
+    """(lat float64[size], lon float64[size]): the pixel centres of slippy-map tile z/x/y (spherical Mercator, the y axis
+    pointing south), degrees -- row i's latitude and column j's longitude, the grid HeatmapEngine.window_raster takes.
+    ValueError for z outside 0..30, x / y outside 0..2**z - 1, size outside 1..4096."""
+    z, x, y, size = int(z), int(x), int(y), int(size)
+    if not 0 <= z <= 30:
+        raise ValueError(f"zoom {z}: 0..30 expected")
+    if not (0 <= x < 2 ** z and 0 <= y < 2 ** z):
+        raise ValueError(f"tile {z}/{x}/{y}: x and y in 0..{2 ** z - 1} expected")
+    if not 1 <= size <= 4096:
+        raise ValueError(f"size {size}: 1..4096 expected")
+    k = (np.arange(size, dtype=np.float64) + 0.5) / size
+    u = (x + k) / 2.0 ** z
+    v = (y + k) / 2.0 ** z
+    lon = u * 360.0 - 180.0
+    lat = np.degrees(np.arctan(np.sinh(np.pi * (1.0 - 2.0 * v))))
+    return lat, lon
+
+
+def png_from_classes(classes, palette=COUNT_PALETTE):
+    """An 8-bit indexed PNG of a uint8[rows, cols] class grid: PLTE + tRNS from palette ((r, g, b, a) per class), one
+    IDAT, filter 0 on every row.  Runs on the host (zlib, struct): a 64 KB tile is not a hot path.  ValueError for an
+    empty grid, a palette of more than 256 entries or a class outside the palette."""
+    import struct
+    import zlib
+    a = np.ascontiguousarray(classes, dtype=np.uint8)
+    if a.ndim != 2 or a.size == 0:
+        raise ValueError("classes: a non-empty 2-D grid expected")
+    pal = [tuple(int(q) for q in p) for p in palette]
+    if not 1 <= len(pal) <= 256 or any(len(p) != 4 or min(p) < 0 or max(p) > 255 for p in pal):
+        raise ValueError("palette: 1..256 entries of (r, g, b, a), each 0..255, expected")
+    if int(a.max()) >= len(pal):
+        raise ValueError(f"class {int(a.max())} outside the palette's {len(pal)} entries")
+    h, w = a.shape
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+    rows = np.zeros((h, w + 1), np.uint8)   # (a filter byte 0 in front of every row)
+    rows[:, 1:] = a
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 3, 0, 0, 0)) +
+            chunk(b"PLTE", bytes(c for p in pal for c in p[:3])) + chunk(b"tRNS", bytes(p[3] for p in pal)) +
+            chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
+
+
+def tiles_latest_png(engine, z, x, y, res=None, size=256):
+    """What a /api/tiles/latest/{z}/{x}/{y}.png route returns: the newest live window's tile z/x/y as an indexed PNG in
+    the reference page's count classes (COUNT_THRESHOLDS, COUNT_PALETTE), every pixel snapped to its H3 cell at
+    resolution res (None: the engine's) and looked up on the GPU.  Which res suits which zoom is the caller's choice."""
+    lat, lon = tile_grid(z, x, y, size)
+    _, classes = engine.window_raster(lat, lon, None, res, COUNT_THRESHOLDS, copy=False)
+    return png_from_classes(classes, COUNT_PALETTE)
