@@ -34,6 +34,7 @@
  *                                   the GPU, byte for byte json.dumps of the collections the reference builds in Python.
  *   hm_window_geojson_view / hm_positions_geojson_view / hm_cells_in_view -- the same for a client's map viewport.
  *   hm_window_raster             -- a live window's counts per pixel of a grid, for z/x/y raster tiles of the heatmap.
+ *   hm_positions_density*        -- the positions state grouped into H3 cells: vehicles per cell at any resolution.
  */
 #ifndef MOBHEAT_H
 #define MOBHEAT_H
@@ -640,6 +641,48 @@ int hm_selftest_window_raster(const hm_state_rec *recs, int64_t n, int32_t res, 
  * latLngToCell handed to the exact path, [2] the records in the roll-up's table (0: the window was not live), [3] its two
  * kernels, microseconds (HIP events). */
 int hm_raster_info(const hm_ctx *ctx, int64_t *v, int32_t n);
+
+/* ---- the positions state S as H3 density cells: how many vehicles are in each cell right now ----
+ * density(S, res, since_us), res 0..15 -- independent of the context's h3_res: positions are raw coordinates.
+ *   kept keys  a key of S is kept iff ts_us >= since_us (a plain int64 compare; INT64_MIN keeps every key).  S is never
+ *              evicted, so since_us is how a reader leaves out vehicles that stopped reporting.
+ *   snapping   each kept key by latLngToCell(lat, lon, res), exactly the cell hm_latlng_to_cell gives.  A key without a
+ *              cell (hm_positions_import does not check coordinates: NaN, |lat| > 90, |lon| > 180) belongs to no group
+ *              and is counted as unsnapped.
+ *   groups     one hm_state_rec per distinct cell, in no particular order: cell; count = the vehicles in it; sum_lat /
+ *              sum_lon = the sums of their stored doubles (fp64 adds in arrival order, as hm_window_rollup's: avg = sum /
+ *              count on the caller's side); n_speed 0, sum_speed +0.0, reserved 0; and window_start_us REUSED for the
+ *              NEWEST ts_us in the group (S has no window; the field tells how fresh a cell's count is).
+ *   view       (optional) a group is kept iff its CELL is in view by hm_cells_in_view's tile rule (the ring's box, pole
+ *              cells, antimeridian) -- not a point test on the vehicles: a hexagon on the view's edge shows its whole
+ *              count, so panning does not change numbers.
+ * An empty S, a since_us newer than every key or a view that meets nothing: *n = 0.  Records are library-owned, in device
+ * or pinned host memory per out_memory (HM_MEM_DEVICE / HM_MEM_HOST), valid until the next hm_positions_* call on the
+ * context; hm_encode_tile_features(..., HM_MEM_DEVICE, recs, ...) on the same context may read the device records (the
+ * encoder has buffers of its own) -- the tile feature is the density's feature.  The calls read S only: S, the tile state,
+ * hm_state_version and a roll-up's table (hm_window_raster) are unaffected, and a repeated call of the same size allocates
+ * nothing.  res outside 0..15, a bad out_memory, an invalid view: HM_E_INVALID, nothing touched.  A shard context
+ * (shard_count > 1): HM_E_UNSUPPORTED, as hm_positions_update.  Between stage calls: HM_E_STATE. */
+int hm_positions_density(hm_ctx *ctx, int32_t res, int64_t since_us, const hm_view *view /* NULL: no filter */,
+                         int32_t out_memory, const hm_state_rec **recs, int64_t *n);
+/* hm_window_raster's grid, thresholds, limits, saturation, classes and outputs (its buffers too); a pixel's value is the
+ * density count of latLngToCell(lat[r], lon[c], res), 0 where no kept vehicle is in that cell.  hm_raster_info afterwards
+ * reports this call ([2]: the density's groups).  Errors as hm_positions_density's and hm_window_raster's grid errors. */
+int hm_positions_density_raster(hm_ctx *ctx, int32_t res, int64_t since_us, const double *lat, int32_t rows,
+                                const double *lon, int32_t cols, const int64_t *thresholds, int32_t n_thresholds,
+                                int32_t out_memory, const uint32_t **counts, const uint8_t **classes);
+/* Host execution of the same per-key code on caller records, no view (no GPU): the groups into out (cap records; *n_out =
+ * their number, HM_E_INVALID if cap does not suffice), *unsnapped (optional) = the kept keys without a cell.  Sums are added
+ * in record order. */
+int hm_selftest_positions_density(const hm_position_rec *recs, int64_t n, int32_t res, int64_t since_us,
+                                  hm_state_rec *out, int64_t cap, int64_t *n_out, int64_t *unsnapped);
+/* up to n of, for the last density call on the context (either entry point): [0] keys scanned, [1] keys kept by since_us,
+ * [2] unsnapped keys, [3] groups before the view, [4] groups returned, [5] keys that took the exact latLngToCell path,
+ * [6] adds into the group-by's global table (spills of the per-workgroup tables plus their final flushes), [7] workgroups
+ * the group-by launched, [8] device time from the first kernel to the last, microseconds (HIP events; with a view the filter kernel's time is
+ * added, the host's read of the group count in between is not), [9] the global
+ * table's slots.  All 0 before the first call. */
+int hm_positions_density_info(const hm_ctx *ctx, int64_t *v, int32_t n);
 
 /* json.dumps(x) of n doubles -- CPython's float.__repr__, NaN / Infinity / -Infinity for the non-finite -- as the GeoJSON
  * encoders write them (csrc/float_repr.h), executed on the host and on GPU `device` (test entry points): value i's

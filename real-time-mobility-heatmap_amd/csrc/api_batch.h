@@ -248,6 +248,7 @@ void hm_destroy(hm_ctx *ctx) {
     positions_free(ctx);
     geojson_free(ctx);
     raster_free(ctx);
+    density_free(ctx);
     for (auto &g : ctx->gens)
         if (!in_arena(ctx, g.tab)) (void)hipFree(g.tab);
     for (auto &pt : ctx->pool)

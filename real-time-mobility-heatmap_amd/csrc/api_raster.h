@@ -22,32 +22,15 @@ static int raster_init(hm_ctx *ctx) {
     return HM_OK;
 }
 
-int hm_window_raster(hm_ctx *ctx, int64_t window_start_us, int32_t res, const double *lat, int32_t rows, const double *lon,
-                     int32_t cols, const int64_t *thresholds, int32_t n_thresholds, int32_t out_memory, const uint32_t **counts,
-                     const uint8_t **classes) {
-    if (!ctx || !counts || (out_memory != HM_MEM_HOST && out_memory != HM_MEM_DEVICE))
-        return ctx ? set_err(ctx, HM_E_INVALID, "bad argument") : HM_E_INVALID;
-    if (const char *why = raster_grid_error(rows, cols)) return set_err(ctx, HM_E_INVALID, "hm_window_raster: %s", why);
-    RasterThr thr;
-    if (!raster_thresholds(thresholds, n_thresholds, thr))
-        return set_err(ctx, HM_E_INVALID, "hm_window_raster: 0..%d thresholds, each >= 0, strictly ascending", RASTER_MAX_THRESHOLDS);
-    if (n_thresholds > 0 && ctx->shard_count > 1)
-        return set_err(ctx, HM_E_INVALID, "hm_window_raster: classes on a shard context (add the ranks' counts, then classify)");
-    if (res < 0 || res > ctx->cfg.h3_res)
-        return set_err(ctx, HM_E_INVALID, "raster resolution %d outside 0..%d", res, ctx->cfg.h3_res);
-    if (ctx->stage != 0) return set_err(ctx, HM_E_STATE, "hm_window_raster between stage calls");
-    const int64_t n = (int64_t)rows * cols;
-    if (n > 0 && (!lat || !lon)) return set_err(ctx, HM_E_INVALID, "bad argument");
-    *counts = nullptr;
-    if (classes) *classes = nullptr;
+// The grid looked up in a group table of nslots GrowRec slots holding m records (m == 0: no table, an all-zero grid):
+// upload lat / lon, k_raster + k_raster_exact, the outputs handed out per out_memory.  R.info[0] is the caller's;
+// [1]-[3] are set here.  Shared by hm_window_raster (the roll-up's table) and hm_positions_density_raster (the density's).
+static int raster_from_table(hm_ctx *ctx, const GrowRec *tab, int64_t nslots, int64_t m, int32_t res, const double *lat, int32_t rows,
+                             const double *lon, int32_t cols, const RasterThr &thr, bool want_classes, int32_t out_memory,
+                             const uint32_t **counts, const uint8_t **classes) {
     hm_ctx::Raster &R = ctx->raster;
-    R.info[0] = n;
-    R.info[1] = R.info[2] = R.info[3] = 0;
-    if (n == 0) return HM_OK;
-    const bool want_classes = n_thresholds > 0 && classes;
-    int64_t m = 0, nslots = 0;
+    const int64_t n = (int64_t)rows * cols;
     int rc;
-    if ((rc = rollup_on_device(ctx, window_start_us, res, "hm_window_raster", &m, &nslots))) return rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if ((rc = raster_init(ctx)) || (rc = ensure(ctx, R.counts, (size_t)n * 4)) ||
         (want_classes && (rc = ensure(ctx, R.classes, (size_t)n))))
@@ -55,7 +38,7 @@ int hm_window_raster(hm_ctx *ctx, int64_t window_start_us, int32_t res, const do
     uint32_t *d_counts = (uint32_t *)R.counts.p;
     uint8_t *d_classes = want_classes ? (uint8_t *)R.classes.p : nullptr;
     R.info[2] = m;
-    if (m == 0) {   // the window is not live: no table to look anything up in
+    if (m == 0) {   // nothing to look anything up in
         HIPCHK(ctx, hipMemsetAsync(d_counts, 0, (size_t)n * 4, ctx->stream));
         if (d_classes) HIPCHK(ctx, hipMemsetAsync(d_classes, 0, (size_t)n, ctx->stream));
     } else {
@@ -66,7 +49,6 @@ int hm_window_raster(hm_ctx *ctx, int64_t window_start_us, int32_t res, const do
         HIPCHK(ctx, hipMemcpyAsync(R.lat.p, lat, (size_t)rows * 8, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipMemcpyAsync(R.lon.p, lon, (size_t)cols * 8, hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(ctx, hipMemsetAsync(n_slow, 0, 8, ctx->stream));
-        const GrowRec *tab = (const GrowRec *)ctx->ru_tab.p;
         const unsigned long long mask = (unsigned long long)(nslots - 1);
         const int64_t nunits = (int64_t)rows * ((cols + 63) / 64);   // a wave each, four to a workgroup
         HIPCHK(ctx, hipEventRecord(R.ev[0], ctx->stream));
@@ -101,6 +83,36 @@ int hm_window_raster(hm_ctx *ctx, int64_t window_start_us, int32_t res, const do
         if (d_classes) *classes = d_classes;
     }
     return HM_OK;
+}
+
+int hm_window_raster(hm_ctx *ctx, int64_t window_start_us, int32_t res, const double *lat, int32_t rows, const double *lon,
+                     int32_t cols, const int64_t *thresholds, int32_t n_thresholds, int32_t out_memory, const uint32_t **counts,
+                     const uint8_t **classes) {
+    if (!ctx || !counts || (out_memory != HM_MEM_HOST && out_memory != HM_MEM_DEVICE))
+        return ctx ? set_err(ctx, HM_E_INVALID, "bad argument") : HM_E_INVALID;
+    if (const char *why = raster_grid_error(rows, cols)) return set_err(ctx, HM_E_INVALID, "hm_window_raster: %s", why);
+    RasterThr thr;
+    if (!raster_thresholds(thresholds, n_thresholds, thr))
+        return set_err(ctx, HM_E_INVALID, "hm_window_raster: 0..%d thresholds, each >= 0, strictly ascending", RASTER_MAX_THRESHOLDS);
+    if (n_thresholds > 0 && ctx->shard_count > 1)
+        return set_err(ctx, HM_E_INVALID, "hm_window_raster: classes on a shard context (add the ranks' counts, then classify)");
+    if (res < 0 || res > ctx->cfg.h3_res)
+        return set_err(ctx, HM_E_INVALID, "raster resolution %d outside 0..%d", res, ctx->cfg.h3_res);
+    if (ctx->stage != 0) return set_err(ctx, HM_E_STATE, "hm_window_raster between stage calls");
+    const int64_t n = (int64_t)rows * cols;
+    if (n > 0 && (!lat || !lon)) return set_err(ctx, HM_E_INVALID, "bad argument");
+    *counts = nullptr;
+    if (classes) *classes = nullptr;
+    hm_ctx::Raster &R = ctx->raster;
+    R.info[0] = n;
+    R.info[1] = R.info[2] = R.info[3] = 0;
+    if (n == 0) return HM_OK;
+    const bool want_classes = n_thresholds > 0 && classes;
+    int64_t m = 0, nslots = 0;
+    int rc;
+    if ((rc = rollup_on_device(ctx, window_start_us, res, "hm_window_raster", &m, &nslots))) return rc;
+    return raster_from_table(ctx, (const GrowRec *)ctx->ru_tab.p, nslots, m, res, lat, rows, lon, cols, thr, want_classes, out_memory,
+                             counts, classes);
 }
 
 // Host execution of the same per-pixel code: the fast path with its hand-over to the exact path, the cell-0 rule, a

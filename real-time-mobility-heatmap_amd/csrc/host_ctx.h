@@ -210,6 +210,17 @@ struct hm_ctx {
         bool ready = false;
         int64_t info[4] = {0, 0, 0, 0};   // hm_raster_info: pixels, exact-path pixels, records in the table, kernel us
     } raster;
+    // hm_positions_density* (api_density.h, k_density.h): the slots' cells, the exception list, the zeroed group table
+    // (not ru_tab: a roll-up's table stays probe-able for hm_window_raster), the compacted records, those in view, the
+    // control words -- buffers of its own.  Nothing here is allocated before the first call.
+    struct Density {
+        DevBuf cell_of, slow, tab, out, vout, words;
+        void *h_recs = nullptr;   // pinned host copy of the records
+        size_t h_recs_cap = 0;
+        hipEvent_t ev[4] = {};    // before k_density_cells, after k_density_emit; before / after the view's k_view_tiles
+        bool ready = false;
+        int64_t info[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // hm_positions_density_info
+    } dens;
     DevBuf keys;                     // k_ingest's event key per row (kernels.h ekey)
     // k_ingest's fused binning (large direct-path batches): the bins' cursors (RP_BINS + 1 u32: the last stays 0, so
     // that their exclusive scan ends with the total) and the slab capacity; the slabs are parts_sorted
@@ -351,6 +362,14 @@ static void raster_free(hm_ctx *ctx) {
     for (void *p : {R.h_counts, R.h_classes})
         if (p) (void)hipHostFree(p);
     for (auto &e : R.ev)
+        if (e) (void)hipEventDestroy(e);
+}
+static void density_free(hm_ctx *ctx) {
+    hm_ctx::Density &D = ctx->dens;
+    for (DevBuf *b : {&D.cell_of, &D.slow, &D.tab, &D.out, &D.vout, &D.words})
+        if (b->p) (void)hipFree(b->p);
+    if (D.h_recs) (void)hipHostFree(D.h_recs);
+    for (auto &e : D.ev)
         if (e) (void)hipEventDestroy(e);
 }
 

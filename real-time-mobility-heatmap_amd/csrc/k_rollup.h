@@ -40,8 +40,10 @@ struct RuTable {
 };
 
 // add a child's aggregate to parent p in the LDS table; false: no slot for it (the caller adds it globally)
+// SLOT (k_density.h, whose table has one more word per slot): *slot = the slot the aggregate went to
+template <bool SLOT = false>
 __device__ __forceinline__ bool ru_lds_add(RuTable &T, uint64_t p, unsigned long long c, unsigned long long ns, double ssp,
-                                           double sla, double slo) {
+                                           double sla, double slo, unsigned *slot = nullptr) {
     unsigned h = (unsigned)(mix64(p) >> 32) & (RU_SLOTS - 1);
     for (int q = 0; q < RU_PROBES; q++) {
         unsigned long long cur = __hip_atomic_load(&T.key[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -58,6 +60,7 @@ __device__ __forceinline__ bool ru_lds_add(RuTable &T, uint64_t p, unsigned long
             }
             atomicAdd(&T.slat[h], sla);
             atomicAdd(&T.slon[h], slo);
+            if constexpr (SLOT) *slot = h;
             return true;
         }
         h = (h + 1) & (RU_SLOTS - 1);
@@ -66,9 +69,11 @@ __device__ __forceinline__ bool ru_lds_add(RuTable &T, uint64_t p, unsigned long
 }
 
 // add an aggregate to parent p in the global table (mask + 1 slots); false: every slot belongs to another parent
-// (cannot happen at load <= 1/2; the bound keeps a mis-sized table from spinning)
+// (cannot happen at load <= 1/2; the bound keeps a mis-sized table from spinning).  SLOT: *slot = the parent's slot
+template <bool SLOT = false>
 __device__ __forceinline__ bool ru_global_add(GrowRec *tab, unsigned long long mask, uint64_t p, unsigned long long c,
-                                              unsigned long long ns, double ssp, double sla, double slo) {
+                                              unsigned long long ns, double ssp, double sla, double slo,
+                                              unsigned long long *slot = nullptr) {
     unsigned long long seen;
     const unsigned long long h = tab_probe<true>([tab](unsigned long long i) { return (unsigned long long *)&tab[i].cell; }, mask,
                                                  mix64(p) & mask, mask + 1, 0ull, p, TabKeyIs{p, 0ull}, seen);
@@ -81,6 +86,7 @@ __device__ __forceinline__ bool ru_global_add(GrowRec *tab, unsigned long long m
     }
     atomicAdd(&s.slat, sla);
     atomicAdd(&s.slon, slo);
+    if constexpr (SLOT) *slot = h;
     return true;
 }
 

@@ -191,6 +191,11 @@ SIGNATURES = {
     "hm_window_raster": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, _P(c_vp), _P(c_vp)]),
     "hm_selftest_window_raster": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp]),
     "hm_raster_info": (c_i32, [c_vp, c_vp, c_i32]),
+    "hm_positions_density": (c_i32, [c_vp, c_i32, c_i64, _P(HmView), c_i32, _P(c_vp), _P(c_i64)]),
+    "hm_positions_density_raster": (c_i32, [c_vp, c_i32, c_i64, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, _P(c_vp),
+                                            _P(c_vp)]),
+    "hm_selftest_positions_density": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_i64, _P(c_i64), _P(c_i64)]),
+    "hm_positions_density_info": (c_i32, [c_vp, c_vp, c_i32]),
     "hm_selftest_float_repr_host": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "hm_selftest_float_repr_device": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32]),
     "hm_abi_version": (c_i32, []),
@@ -516,6 +521,20 @@ def float_repr_selftest(x, device=None):
     return text, ln
 
 
+def wall_iso(us, tz=None):
+    """The text the read side writes for a time: isoformat of the naive local wall time of us microseconds (pyspark's
+    naive datetimes, stream._spark_datetime), or of zone tz's wall time; "" for None."""
+    if us is None:
+        return ""
+    import datetime as _dt
+
+    from .stream import _spark_datetime
+    us = int(us)
+    if tz is None:
+        return _spark_datetime(us).isoformat()
+    return _dt.datetime.fromtimestamp(us // 1000000, tz).replace(tzinfo=None, microsecond=us % 1000000).isoformat()
+
+
 def geojson_cfg(window_start_text, window_end_text):
     """hm_geojson_cfg for the two window texts (str or bytes); the returned tuple keeps the bytes alive."""
     a = window_start_text.encode("utf-8") if isinstance(window_start_text, str) else bytes(window_start_text)
@@ -601,6 +620,22 @@ def raster_args(lat, lon, thresholds):
     return lat, lon, thr
 
 
+def raster_grids(pc, pk, lat, lon, thr, copy):
+    """The outputs of a raster call (host pointers pc / pk) as counts uint32[rows, cols], or (counts, classes uint8[rows,
+    cols]) when thresholds were given; zeros where the call wrote nothing; copy=False: views of the library's buffers."""
+    shape, n = (lat.size, lon.size), lat.size * lon.size
+
+    def grid(p, ct, dt):
+        if n == 0 or not p:
+            return np.zeros(shape, dt)
+        a = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ct)), shape=(n,)).reshape(shape)
+        return a.copy() if copy else a
+    counts = grid(pc, ctypes.c_uint32, np.uint32)
+    if thr is None:
+        return counts
+    return counts, (grid(pk, ctypes.c_uint8, np.uint8) if thr.size else np.zeros(shape, np.uint8))
+
+
 def window_raster_selftest(recs, res, lat, lon, thresholds=None):
     """Host execution of the raster's per-pixel code (no GPU) on STATE_REC_DTYPE records: counts uint32[rows, cols], or
     (counts, classes uint8[rows, cols]) when thresholds are given."""
@@ -614,3 +649,22 @@ def window_raster_selftest(recs, res, lat, lon, thresholds=None):
                                         ptr(counts), None if classes is None else ptr(classes)), None,
           "hm_selftest_window_raster")
     return counts if thr is None else (counts, classes)
+
+
+# ---- the positions state as H3 density cells (csrc/k_density.h) ----
+INT64_MIN = -(1 << 63)
+
+
+def positions_density_selftest(recs, res, since_us=None, cap=None):
+    """Host execution of the density's per-key code (no GPU) on POSITION_REC_DTYPE records: (STATE_REC_DTYPE records, one
+    per distinct cell among the keys with ts_us >= since_us (None: every key), window_start_us = the group's newest ts_us;
+    the kept keys without a cell).  cap: room for that many groups (None: one per record); too few raise HM_E_INVALID."""
+    lib = load()
+    recs = np.ascontiguousarray(recs, dtype=POSITION_REC_DTYPE)
+    cap = recs.size if cap is None else int(cap)
+    out = np.zeros(max(cap, 1), STATE_REC_DTYPE)
+    n, bad = c_i64(), c_i64()
+    check(lib.hm_selftest_positions_density(ptr(recs) if recs.size else None, recs.size, int(res),
+                                            INT64_MIN if since_us is None else int(since_us), ptr(out), cap,
+                                            ctypes.byref(n), ctypes.byref(bad)), None, "hm_selftest_positions_density")
+    return out[:n.value].copy(), int(bad.value)

@@ -317,17 +317,7 @@ class HeatmapEngine:
                                          None if thr is None else ptr(thr), 0 if thr is None else thr.size, HM_MEM_HOST,
                                          ctypes.byref(pc), ctypes.byref(pk) if thr is not None else None),
               self._ctx, "hm_window_raster")
-        shape, n = (lat.size, lon.size), lat.size * lon.size
-
-        def grid(p, ct, dt):
-            if n == 0 or not p:
-                return np.zeros(shape, dt)
-            a = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ct)), shape=(n,)).reshape(shape)
-            return a.copy() if copy else a
-        counts = grid(pc, ctypes.c_uint32, np.uint32)
-        if thr is None:
-            return counts
-        return counts, (grid(pk, ctypes.c_uint8, np.uint8) if thr.size else np.zeros(shape, np.uint8))
+        return _lib.raster_grids(pc, pk, lat, lon, thr, copy)
 
     def raster_info(self):
         v = (ctypes.c_int64 * 4)()
@@ -349,21 +339,12 @@ class HeatmapEngine:
         valid until the next call on this engine.  with_records: (body, records in feature order, offsets) instead.
         view=(west, south, east, north) in degrees: only the tiles whose boundary box meets the view, filtered on the GPU
         between the roll-up and the encoder (hm_window_geojson_view; west > east crosses the antimeridian)."""
-        import datetime as _dt
-
-        from .stream import _spark_datetime
-
-        def when(us):
-            us = int(us)
-            if tz is None:
-                return _spark_datetime(us).isoformat()
-            return _dt.datetime.fromtimestamp(us // 1000000, tz).replace(tzinfo=None, microsecond=us % 1000000).isoformat()
         res = self.h3_res if res is None else int(res)
         if window_start_us is None:
             ws, _ = self.live_windows()
             window_start_us = ws[-1] if ws.size else 0
         window_start_us = int(window_start_us)
-        cfg, keep = _lib.geojson_cfg(when(window_start_us), when(window_start_us + self.tile_us))
+        cfg, keep = _lib.geojson_cfg(_lib.wall_iso(window_start_us, tz), _lib.wall_iso(window_start_us + self.tile_us, tz))
         pb, po, pr, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
         if view is None:
             check(self._lib.hm_window_geojson(self._ctx, window_start_us, res, ctypes.byref(cfg), HM_MEM_HOST, ctypes.byref(pb),
@@ -645,6 +626,75 @@ class HeatmapEngine:
         check(self._lib.hm_positions_info(self._ctx, v, 10), self._ctx, "hm_positions_info")
         return {"keys": v[0], "capacity": v[1], "providers": v[2], "vehicles": v[3], "arena_bytes": v[4], "regrows": v[5],
                 "pair_regrows": v[6], "vehicle_arena_regrows": v[7], "update_us": v[8], "update_kernels_us": v[9]}
+
+    # ---- the positions state as H3 density cells (hm_positions_density*; csrc/k_density.h) ----
+    def _density_device(self, res, since_us, view, memory):
+        """hm_positions_density: (pointer of the records in `memory`, their number)"""
+        res = self.h3_res if res is None else int(res)
+        since = _lib.INT64_MIN if since_us is None else int(since_us)
+        v = None if view is None else _lib.view_struct(view)
+        p, n = ctypes.c_void_p(), ctypes.c_int64()
+        check(self._lib.hm_positions_density(self._ctx, res, since, None if v is None else ctypes.byref(v), int(memory),
+                                             ctypes.byref(p), ctypes.byref(n)), self._ctx, "hm_positions_density")
+        return p, n.value
+
+    def positions_density(self, res=None, since_us=None, view=None, copy=True):
+        """How many vehicles of the positions state are in each H3 cell of resolution res (0..15; None: h3_res) right now,
+        among those with ts_us >= since_us (None: all of them): STATE_REC_DTYPE records, one per distinct cell, in no
+        particular order -- count, sum_lat / sum_lon of the stored coordinates, and window_start_us reused for the NEWEST
+        ts_us in the cell (n_speed, sum_speed, reserved 0).  Snapped and grouped on the GPU in one call.  A vehicle whose
+        coordinates have no cell (NaN, out of range) is in no group (positions_density_info()["unsnapped"]).
+        view=(west, south, east, north): only the cells whose boundary box meets the view (readside.ring_in_view's rule,
+        on the cell, not the vehicles).  copy=False: a view of the library's pinned buffer, valid until the next positions
+        call on this engine."""
+        p, n = self._density_device(res, since_us, view, HM_MEM_HOST)
+        if n == 0:
+            return np.zeros(0, STATE_REC_DTYPE)
+        raw = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)), shape=(n * STATE_REC_DTYPE.itemsize,))
+        recs = raw.view(STATE_REC_DTYPE)
+        return recs.copy() if copy else recs
+
+    def positions_density_geojson(self, res=None, since_us=None, tz=None, as_of_us=None, copy=True, with_records=False, *,
+                                  view=None):
+        """The body of a /api/positions/density route: json.dumps(readside.positions_density_from_engine(...),
+        separators=(",", ":")) as bytes -- the density's records never leave the device between the group-by and the tile
+        feature encoder (hm_positions_density with HM_MEM_DEVICE, then hm_encode_tile_features).  windowStart is the
+        isoformat of since_us and windowEnd that of as_of_us (the caller's "now"), formatted as window_geojson formats its
+        window (stream._spark_datetime, or zone tz's wall time); "" where the argument is None.  copy / with_records / view
+        as window_geojson."""
+        cfg, keep = _lib.geojson_cfg(_lib.wall_iso(since_us, tz), _lib.wall_iso(as_of_us, tz))
+        p, n = self._density_device(res, since_us, view, HM_MEM_DEVICE)
+        recs = np.zeros(n, STATE_REC_DTYPE)
+        if with_records and n:   # (the records in feature order, copied back from the device)
+            check(self._lib.hm_memcpy(ptr(recs), p, recs.nbytes, 1), None, "hm_memcpy")
+        pb, po = ctypes.c_void_p(), ctypes.c_void_p()
+        check(self._lib.hm_encode_tile_features(self._ctx, ctypes.byref(cfg), n, HM_MEM_DEVICE, p if n else None, HM_MEM_HOST,
+                                                ctypes.byref(pb), ctypes.byref(po)), self._ctx, "hm_encode_tile_features")
+        body = self._geojson_body(pb, po, n, copy)
+        if not with_records:
+            return body
+        offs = np.ctypeslib.as_array(ctypes.cast(po, ctypes.POINTER(ctypes.c_int64)), shape=(n + 1,)).copy()
+        return body, recs, offs
+
+    def positions_density_raster(self, lat, lon, res=None, since_us=None, thresholds=None, copy=True):
+        """window_raster for the positions density: counts uint32[rows, cols] over the grid lat[rows] x lon[cols], a pixel's
+        value the number of vehicles (ts_us >= since_us) in the cell of resolution res that contains its centre;
+        thresholds: (counts, classes) as window_raster."""
+        res = self.h3_res if res is None else int(res)
+        since = _lib.INT64_MIN if since_us is None else int(since_us)
+        lat, lon, thr = _lib.raster_args(lat, lon, thresholds)
+        pc, pk = ctypes.c_void_p(), ctypes.c_void_p()
+        check(self._lib.hm_positions_density_raster(self._ctx, res, since, ptr(lat), lat.size, ptr(lon), lon.size,
+                                                    None if thr is None else ptr(thr), 0 if thr is None else thr.size,
+                                                    HM_MEM_HOST, ctypes.byref(pc), ctypes.byref(pk) if thr is not None else None),
+              self._ctx, "hm_positions_density_raster")
+        return _lib.raster_grids(pc, pk, lat, lon, thr, copy)
+
+    def positions_density_info(self):
+        v = (ctypes.c_int64 * 10)()
+        check(self._lib.hm_positions_density_info(self._ctx, v, 10), self._ctx, "hm_positions_density_info")
+        return {"keys": v[0], "kept": v[1], "unsnapped": v[2], "groups": v[3], "returned": v[4], "exact_keys": v[5],
+                "global_adds": v[6], "workgroups": v[7], "device_us": v[8], "table_slots": v[9]}
 
     def encode_tile_updates_device(self, city, ttl_minutes):
         """The same, left on the device: (device pointer of the bytes, of the offsets, n statements)."""

@@ -316,3 +316,38 @@ def tiles_latest_png(engine, z, x, y, res=None, size=256):
     lat, lon = tile_grid(z, x, y, size)
     _, classes = engine.window_raster(lat, lon, None, res, COUNT_THRESHOLDS, copy=False)
     return png_from_classes(classes, COUNT_PALETTE)
+
+
+# ---- the positions state as density cells (HeatmapEngine.positions_density, csrc/k_density.h) ----
+def positions_density_from_engine(engine, res=None, since_us=None, tz=None, as_of_us=None, view=None):
+    """The FeatureCollection a /api/positions/density?res=&since=&bbox= route returns: one tile feature (the shape of
+    tiles_latest_collection, so the reference page's tilesLayer colours it by properties.count as it is) per H3 cell of
+    resolution res that holds a vehicle of the engine's positions state seen since since_us -- cellId, count,
+    avgSpeedKmh 0.0 (positions carry no speed), windowStart = since_us and windowEnd = as_of_us (the caller's "now") as
+    tile_docs_from_engine formats a window's bounds, "" for None, and the cell's ring.  view: only the cells whose ring
+    meets it, filtered here in Python (ring_in_view).  The comparison form of positions_density_body."""
+    recs = engine.positions_density(res, since_us)
+    ws, we = _lib.wall_iso(since_us, tz), _lib.wall_iso(as_of_us, tz)
+    geoms = rings([int(c) for c in recs["cell"]], engine.device)
+    features = []
+    for r, ring in zip(recs, geoms):
+        props = {"cellId": format(int(r["cell"]), "x"), "count": int(r["count"]), "avgSpeedKmh": 0.0, "windowStart": ws,
+                 "windowEnd": we}
+        features.append({"type": "Feature", "geometry": {"type": "Polygon", "coordinates": [ring]}, "properties": props})
+    fc = {"type": "FeatureCollection", "features": features}
+    return fc if view is None else _tile_features_in_view(fc, view)
+
+
+def positions_density_body(engine, res=None, since_us=None, tz=None, as_of_us=None, view=None):
+    """The same response as bytes: json.dumps(positions_density_from_engine(...), separators=(",", ":")) up to the order of
+    the features, grouped, filtered and encoded on the GPU (HeatmapEngine.positions_density_geojson)."""
+    return engine.positions_density_geojson(res, since_us, tz, as_of_us, view=view)
+
+
+def positions_density_png(engine, z, x, y, res=None, since_us=None, size=256):
+    """What a /api/positions/density/{z}/{x}/{y}.png route returns: tile z/x/y of the positions density as an indexed PNG
+    in the reference page's count classes (COUNT_THRESHOLDS, COUNT_PALETTE), every pixel snapped to its H3 cell at
+    resolution res (None: the engine's) and looked up on the GPU."""
+    lat, lon = tile_grid(z, x, y, size)
+    _, classes = engine.positions_density_raster(lat, lon, res, since_us, COUNT_THRESHOLDS, copy=False)
+    return png_from_classes(classes, COUNT_PALETTE)
