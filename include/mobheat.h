@@ -684,6 +684,56 @@ int hm_selftest_positions_density(const hm_position_rec *recs, int64_t n, int32_
  * table's slots.  All 0 before the first call. */
 int hm_positions_density_info(const hm_ctx *ctx, int64_t *v, int32_t n);
 
+/* ---- top-k hotspots: the k records with the largest count, in rank order, selected and ordered on the GPU ----
+ * The order: record a ranks before record b iff, lexicographically,
+ *   1. a.count > b.count, counts compared as int64 (the library's own records have count >= 1; caller records may hold 0
+ *      or negative counts);
+ *   2. a.cell < b.cell as uint64;
+ *   3. a has the lower input index (decides only among caller records with repeated (count, cell); roll-up and density
+ *      records have distinct cells).
+ * Only count and cell are read; top(recs, k) = the first min(k, n) records of that order, in that order, each returned
+ * whole and unchanged, bit for bit.  k is 0..HM_TOP_MAX (a contract limit: no page draws more); k < 0 or k > HM_TOP_MAX:
+ * HM_E_INVALID, nothing touched.  k == 0 or no candidate: HM_OK with *n = 0.
+ * Outputs are library-owned, in device or pinned host memory per out_memory (HM_MEM_DEVICE / HM_MEM_HOST), valid until
+ * the next call on the context; the top has buffers of its own (a checkpoint export in progress, a streamed statement
+ * encode and the GeoJSON encoder's buffers are unaffected).  The calls read state only: hm_state_version, the tile
+ * state and the positions state are untouched, and a repeated call of the same size allocates nothing.  Between stage
+ * calls: HM_E_STATE. */
+#define HM_TOP_MAX 65536
+/* top(recs[0, n), k) of caller records in host or device memory per `memory` (as hm_encode_tile_features takes them; n at
+ * most 2^31; device records 16-byte aligned).  Allowed on a shard context: a sharded caller adds the ranks' records of
+ * equal cell and ranks the sums here. */
+int hm_top_records(hm_ctx *ctx, const hm_state_rec *recs, int64_t n, int32_t memory, int64_t k, int32_t out_memory,
+                   const hm_state_rec **top, int64_t *n_top);
+/* top(hm_window_rollup(window_start_us, res) [cut to view, hm_window_geojson_view's rule], k): the view is applied
+ * before the selection, so the result is the busiest tiles in view.  hm_window_rollup's validity rules and errors,
+ * HM_E_INVALID for an invalid view; a window that is not live: *n = 0.  A shard context (shard_count > 1):
+ * HM_E_UNSUPPORTED -- a rank's own top-k is not the global one when a parent's children are spread over ranks. */
+int hm_window_top(hm_ctx *ctx, int64_t window_start_us, int32_t res, const hm_view *view /* NULL: no filter */, int64_t k,
+                  int32_t out_memory, const hm_state_rec **recs, int64_t *n);
+/* The same, then the selected records' features in rank order by hm_window_geojson's encoder, the records never leaving
+ * the device: body, offsets and *n as hm_window_geojson's (none selected: the 42-byte empty body); recs (optional): the
+ * records in feature order, pinned host memory.  Errors as hm_window_top's and hm_window_geojson's. */
+int hm_window_geojson_top(hm_ctx *ctx, int64_t window_start_us, int32_t res, const hm_geojson_cfg *cfg,
+                          const hm_view *view /* NULL: no filter */, int64_t k, int32_t out_memory, const uint8_t **bytes,
+                          const int64_t **offsets, int64_t *n, const hm_state_rec **recs);
+/* top(hm_positions_density(res, since_us, view), k): the density's groups, selected and ranked (window_start_us keeps
+ * its reused meaning, the cell's newest ts_us).  hm_positions_density's errors (a shard context: HM_E_UNSUPPORTED).  The
+ * GeoJSON form is hm_encode_tile_features(..., HM_MEM_DEVICE, recs, ...) on the ranked device records: the features come
+ * out in rank order. */
+int hm_positions_density_top(hm_ctx *ctx, int32_t res, int64_t since_us, const hm_view *view /* NULL: no filter */,
+                             int64_t k, int32_t out_memory, const hm_state_rec **recs, int64_t *n);
+/* Host execution of the select and the ordering with the kernels' own key, digit and comparator code (no GPU):
+ * top(recs, k) into out (room for min(k, n) records), *n_out = min(k, n). */
+int hm_selftest_top_records(const hm_state_rec *recs, int64_t n, int64_t k, hm_state_rec *out, int64_t *n_out);
+/* up to n of, for the last top call on the context: [0] candidates (after the view), [1] records returned, [2] select
+ * passes that examined a byte of the count, [3] of the cell, [4] of the input index, [5] the candidates still tied with
+ * the threshold when the select stopped -- all of them are taken, so this is also what was still needed then, [6] device
+ * time of the top's own kernels from the key extraction to the ordered records, microseconds (HIP events; the host's
+ * read-backs between the passes are not counted, nor are the roll-up, the density or the view filter).  All 0 before
+ * the first call. */
+int hm_top_info(const hm_ctx *ctx, int64_t *v, int32_t n);
+
 /* json.dumps(x) of n doubles -- CPython's float.__repr__, NaN / Infinity / -Infinity for the non-finite -- as the GeoJSON
  * encoders write them (csrc/float_repr.h), executed on the host and on GPU `device` (test entry points): value i's
  * len[i] <= 24 bytes at text[24 i]. */

@@ -149,6 +149,9 @@ int hm_create(const hm_config *cfg, hm_ctx **out) {
     // (phase_table)
     if (const char *m = getenv("MOBHEAT_TEST_AGG_GRID")) ctx->test_agg_grid = std::max(0, atoi(m));
     if (const char *m = getenv("MOBHEAT_TEST_AGG_CAP")) ctx->test_agg_cap = (unsigned)std::max(0, atoi(m));
+    // MOBHEAT_TEST_TOP_GRID (tests): at most that many workgroups in the top's streaming kernels (keys, passes,
+    // compaction), so that a few thousand records are several grid-stride iterations of every workgroup (top_on_device)
+    if (const char *m = getenv("MOBHEAT_TEST_TOP_GRID")) ctx->top.test_grid = std::max(0, atoi(m));
     // the registry, its census and the batch statistics side by side (one reset, one readback after k_ingest)
     if (hipMalloc(&ctx->d_wreg, REG_BLOCK_BYTES) != hipSuccess || !(ctx->d_wcount = ctx->d_wreg + WREG_SLOTS + 1) ||
         !(ctx->d_st = (DevStats *)(ctx->d_wreg + 2 * (WREG_SLOTS + 1))) ||
@@ -249,6 +252,7 @@ void hm_destroy(hm_ctx *ctx) {
     geojson_free(ctx);
     raster_free(ctx);
     density_free(ctx);
+    top_free(ctx);
     for (auto &g : ctx->gens)
         if (!in_arena(ctx, g.tab)) (void)hipFree(g.tab);
     for (auto &pt : ctx->pool)

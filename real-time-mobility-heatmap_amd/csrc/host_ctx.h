@@ -221,6 +221,20 @@ struct hm_ctx {
         bool ready = false;
         int64_t info[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // hm_positions_density_info
     } dens;
+    // hm_top_records / hm_window_top / hm_window_geojson_top / hm_positions_density_top (api_top.h, k_top.h): the
+    // candidates' key words, the selected keys with their indices and ranks, the records in rank order, a host input's
+    // device copy, the window's records in view, the control words -- buffers of its own.  Nothing here is allocated
+    // before the first call.
+    struct Top {
+        DevBuf kc, cell, skc, scell, sidx, rank, out, in, vrecs, words;
+        void *h_out = nullptr;    // pinned host copy of the ranked records
+        size_t h_out_cap = 0;
+        unsigned long long h_words[TW_WORDS] = {};   // the control block's initial value, uploaded by every call
+        hipEvent_t ev[2] = {};    // around the kernels between two host reads
+        bool ready = false;
+        int64_t info[7] = {0, 0, 0, 0, 0, 0, 0};   // hm_top_info
+        int test_grid = 0;        // MOBHEAT_TEST_TOP_GRID: the streaming kernels' largest grid (tests; 0: unset)
+    } top;
     DevBuf keys;                     // k_ingest's event key per row (kernels.h ekey)
     // k_ingest's fused binning (large direct-path batches): the bins' cursors (RP_BINS + 1 u32: the last stays 0, so
     // that their exclusive scan ends with the total) and the slab capacity; the slabs are parts_sorted
@@ -370,6 +384,14 @@ static void density_free(hm_ctx *ctx) {
         if (b->p) (void)hipFree(b->p);
     if (D.h_recs) (void)hipHostFree(D.h_recs);
     for (auto &e : D.ev)
+        if (e) (void)hipEventDestroy(e);
+}
+static void top_free(hm_ctx *ctx) {
+    hm_ctx::Top &T = ctx->top;
+    for (DevBuf *b : {&T.kc, &T.cell, &T.skc, &T.scell, &T.sidx, &T.rank, &T.out, &T.in, &T.vrecs, &T.words})
+        if (b->p) (void)hipFree(b->p);
+    if (T.h_out) (void)hipHostFree(T.h_out);
+    for (auto &e : T.ev)
         if (e) (void)hipEventDestroy(e);
 }
 

@@ -17,6 +17,7 @@
 //   k_view.h        read side: a map viewport applied to cells, roll-up records and positions (k_cells_in_view, k_view_tiles)
 //   k_raster.h      read side: a window's counts over a pixel grid, each pixel snapped to its cell (k_raster, k_raster_exact)
 //   k_density.h     read side: the positions state grouped into H3 density cells (k_density_cells, k_density_group)
+//   k_top.h         read side: the k records with the largest count in rank order (k_top_keys, k_top_hist, k_top_rank)
 //   host_ctx.h      the context, allocation, per-window tables, launchers;  host_batch.h: the batch phases
 //   api_*.h         the C ABI of include/mobheat.h (batch, UDF/read side, stage API, checkpoint, sink, JSON, window reads, positions, GeoJSON, viewport, self-tests)
 //
@@ -94,6 +95,7 @@ static hipError_t upload_tables() {
 #include "k_view.h"
 #include "k_raster.h"
 #include "k_density.h"
+#include "k_top.h"
 #include "host_ctx.h"
 #include "host_batch.h"
 #include "host_pipe.h"
@@ -112,6 +114,7 @@ extern "C" {
 #include "api_view.h"
 #include "api_raster.h"
 #include "api_density.h"
+#include "api_top.h"
 #include "api_selftest.h"
 
 }  // extern "C"

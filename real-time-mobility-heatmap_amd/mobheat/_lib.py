@@ -196,6 +196,13 @@ SIGNATURES = {
                                             _P(c_vp)]),
     "hm_selftest_positions_density": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_i64, _P(c_i64), _P(c_i64)]),
     "hm_positions_density_info": (c_i32, [c_vp, c_vp, c_i32]),
+    "hm_top_records": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_i32, _P(c_vp), _P(c_i64)]),
+    "hm_window_top": (c_i32, [c_vp, c_i64, c_i32, _P(HmView), c_i64, c_i32, _P(c_vp), _P(c_i64)]),
+    "hm_window_geojson_top": (c_i32, [c_vp, c_i64, c_i32, _P(HmGeojsonCfg), _P(HmView), c_i64, c_i32, _P(c_vp), _P(c_vp),
+                                      _P(c_i64), _P(c_vp)]),
+    "hm_positions_density_top": (c_i32, [c_vp, c_i32, c_i64, _P(HmView), c_i64, c_i32, _P(c_vp), _P(c_i64)]),
+    "hm_selftest_top_records": (c_i32, [c_vp, c_i64, c_i64, c_vp, _P(c_i64)]),
+    "hm_top_info": (c_i32, [c_vp, c_vp, c_i32]),
     "hm_selftest_float_repr_host": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "hm_selftest_float_repr_device": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32]),
     "hm_abi_version": (c_i32, []),
@@ -668,3 +675,27 @@ def positions_density_selftest(recs, res, since_us=None, cap=None):
                                             INT64_MIN if since_us is None else int(since_us), ptr(out), cap,
                                             ctypes.byref(n), ctypes.byref(bad)), None, "hm_selftest_positions_density")
     return out[:n.value].copy(), int(bad.value)
+
+
+# ---- top-k hotspots (csrc/k_top.h) ----
+HM_TOP_MAX = 65536
+
+
+def top_records_selftest(recs, k):
+    """Host execution of the top's select and ordering (no GPU) on STATE_REC_DTYPE records: the first min(k, n) records of
+    the order (count descending as int64, then cell ascending, then input index), whole."""
+    lib = load()
+    recs = np.ascontiguousarray(recs, dtype=STATE_REC_DTYPE)
+    out = np.zeros(max(min(int(k), recs.size), 1), STATE_REC_DTYPE)
+    n = c_i64()
+    check(lib.hm_selftest_top_records(ptr(recs) if recs.size else None, recs.size, int(k), ptr(out), ctypes.byref(n)), None,
+          "hm_selftest_top_records")
+    return out[:n.value].copy()
+
+
+def state_recs_at(p, n, copy=True):
+    """n hm_state_rec at host pointer p as a STATE_REC_DTYPE array (a copy, or a view of the library's buffer)."""
+    if n == 0:
+        return np.zeros(0, STATE_REC_DTYPE)
+    recs = np.ctypeslib.as_array(ctypes.cast(p, _P(ctypes.c_uint8)), shape=(n * STATE_REC_DTYPE.itemsize,)).view(STATE_REC_DTYPE)
+    return recs.copy() if copy else recs

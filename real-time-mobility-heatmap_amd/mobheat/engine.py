@@ -331,14 +331,16 @@ class HeatmapEngine:
         raw = np.ctypeslib.as_array(ctypes.cast(pb, ctypes.POINTER(ctypes.c_uint8)), shape=(_lib.geojson_body_len(offs),))
         return raw.tobytes() if copy else memoryview(raw)
 
-    def window_geojson(self, window_start_us=None, res=None, tz=None, copy=True, with_records=False, *, view=None):
+    def window_geojson(self, window_start_us=None, res=None, tz=None, copy=True, with_records=False, *, view=None, top=None):
         """The body of /api/tiles/latest for one live window (None: the newest) at H3 resolution res <= h3_res (None:
         h3_res): json.dumps(readside.tiles_latest_collection(...), separators=(",", ":")) as bytes, rolled up and
         encoded on the GPU in one call.  windowStart / windowEnd are formatted as readside.tile_docs_from_engine formats
         them (stream._spark_datetime, or zone tz's wall time).  copy=False: a memoryview of the library's pinned buffer,
         valid until the next call on this engine.  with_records: (body, records in feature order, offsets) instead.
         view=(west, south, east, north) in degrees: only the tiles whose boundary box meets the view, filtered on the GPU
-        between the roll-up and the encoder (hm_window_geojson_view; west > east crosses the antimeridian)."""
+        between the roll-up and the encoder (hm_window_geojson_view; west > east crosses the antimeridian).
+        top=k (0..65536): only the k tiles with the largest count (in view, when there is one), the features in rank
+        order -- count descending, then cell ascending (hm_window_geojson_top)."""
         res = self.h3_res if res is None else int(res)
         if window_start_us is None:
             ws, _ = self.live_windows()
@@ -346,7 +348,14 @@ class HeatmapEngine:
         window_start_us = int(window_start_us)
         cfg, keep = _lib.geojson_cfg(_lib.wall_iso(window_start_us, tz), _lib.wall_iso(window_start_us + self.tile_us, tz))
         pb, po, pr, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
-        if view is None:
+        if top is not None:
+            v = None if view is None else _lib.view_struct(view)
+            check(self._lib.hm_window_geojson_top(self._ctx, window_start_us, res, ctypes.byref(cfg),
+                                                  None if v is None else ctypes.byref(v), int(top), HM_MEM_HOST,
+                                                  ctypes.byref(pb), ctypes.byref(po), ctypes.byref(n),
+                                                  ctypes.byref(pr) if with_records else None),
+                  self._ctx, "hm_window_geojson_top")
+        elif view is None:
             check(self._lib.hm_window_geojson(self._ctx, window_start_us, res, ctypes.byref(cfg), HM_MEM_HOST, ctypes.byref(pb),
                                               ctypes.byref(po), ctypes.byref(n), ctypes.byref(pr) if with_records else None),
                   self._ctx, "hm_window_geojson")
@@ -628,17 +637,22 @@ class HeatmapEngine:
                 "pair_regrows": v[6], "vehicle_arena_regrows": v[7], "update_us": v[8], "update_kernels_us": v[9]}
 
     # ---- the positions state as H3 density cells (hm_positions_density*; csrc/k_density.h) ----
-    def _density_device(self, res, since_us, view, memory):
-        """hm_positions_density: (pointer of the records in `memory`, their number)"""
+    def _density_device(self, res, since_us, view, memory, top=None):
+        """hm_positions_density (top=k: hm_positions_density_top): (pointer of the records in `memory`, their number)"""
         res = self.h3_res if res is None else int(res)
         since = _lib.INT64_MIN if since_us is None else int(since_us)
         v = None if view is None else _lib.view_struct(view)
         p, n = ctypes.c_void_p(), ctypes.c_int64()
+        if top is not None:
+            check(self._lib.hm_positions_density_top(self._ctx, res, since, None if v is None else ctypes.byref(v), int(top),
+                                                     int(memory), ctypes.byref(p), ctypes.byref(n)),
+                  self._ctx, "hm_positions_density_top")
+            return p, n.value
         check(self._lib.hm_positions_density(self._ctx, res, since, None if v is None else ctypes.byref(v), int(memory),
                                              ctypes.byref(p), ctypes.byref(n)), self._ctx, "hm_positions_density")
         return p, n.value
 
-    def positions_density(self, res=None, since_us=None, view=None, copy=True):
+    def positions_density(self, res=None, since_us=None, view=None, copy=True, *, top=None):
         """How many vehicles of the positions state are in each H3 cell of resolution res (0..15; None: h3_res) right now,
         among those with ts_us >= since_us (None: all of them): STATE_REC_DTYPE records, one per distinct cell, in no
         particular order -- count, sum_lat / sum_lon of the stored coordinates, and window_start_us reused for the NEWEST
@@ -646,8 +660,9 @@ class HeatmapEngine:
         coordinates have no cell (NaN, out of range) is in no group (positions_density_info()["unsnapped"]).
         view=(west, south, east, north): only the cells whose boundary box meets the view (readside.ring_in_view's rule,
         on the cell, not the vehicles).  copy=False: a view of the library's pinned buffer, valid until the next positions
-        call on this engine."""
-        p, n = self._density_device(res, since_us, view, HM_MEM_HOST)
+        call on this engine.  top=k (0..65536): only the k cells with the most vehicles (in view, when there is one), in
+        rank order -- count descending, then cell ascending (hm_positions_density_top)."""
+        p, n = self._density_device(res, since_us, view, HM_MEM_HOST, top)
         if n == 0:
             return np.zeros(0, STATE_REC_DTYPE)
         raw = np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctypes.c_uint8)), shape=(n * STATE_REC_DTYPE.itemsize,))
@@ -655,15 +670,16 @@ class HeatmapEngine:
         return recs.copy() if copy else recs
 
     def positions_density_geojson(self, res=None, since_us=None, tz=None, as_of_us=None, copy=True, with_records=False, *,
-                                  view=None):
+                                  view=None, top=None):
         """The body of a /api/positions/density route: json.dumps(readside.positions_density_from_engine(...),
         separators=(",", ":")) as bytes -- the density's records never leave the device between the group-by and the tile
         feature encoder (hm_positions_density with HM_MEM_DEVICE, then hm_encode_tile_features).  windowStart is the
         isoformat of since_us and windowEnd that of as_of_us (the caller's "now"), formatted as window_geojson formats its
         window (stream._spark_datetime, or zone tz's wall time); "" where the argument is None.  copy / with_records / view
-        as window_geojson."""
+        as window_geojson.  top=k: the k cells with the most vehicles, the features in rank order (the ranked device
+        records of hm_positions_density_top go to the same encoder)."""
         cfg, keep = _lib.geojson_cfg(_lib.wall_iso(since_us, tz), _lib.wall_iso(as_of_us, tz))
-        p, n = self._density_device(res, since_us, view, HM_MEM_DEVICE)
+        p, n = self._density_device(res, since_us, view, HM_MEM_DEVICE, top)
         recs = np.zeros(n, STATE_REC_DTYPE)
         if with_records and n:   # (the records in feature order, copied back from the device)
             check(self._lib.hm_memcpy(ptr(recs), p, recs.nbytes, 1), None, "hm_memcpy")
@@ -695,6 +711,38 @@ class HeatmapEngine:
         check(self._lib.hm_positions_density_info(self._ctx, v, 10), self._ctx, "hm_positions_density_info")
         return {"keys": v[0], "kept": v[1], "unsnapped": v[2], "groups": v[3], "returned": v[4], "exact_keys": v[5],
                 "global_adds": v[6], "workgroups": v[7], "device_us": v[8], "table_slots": v[9]}
+
+    # ---- top-k hotspots: the k records with the largest count in rank order (hm_top_*; csrc/k_top.h) ----
+    def top_records(self, recs, k):
+        """The first min(k, n) of STATE_REC_DTYPE records recs in the order count descending (int64), then cell ascending
+        (uint64), then input index -- selected and ordered on the GPU, each record whole (hm_top_records; readside.top_of
+        is the numpy form).  k is 0..65536.  Works on a shard engine: add the ranks' records of equal cell, then rank."""
+        recs = np.ascontiguousarray(recs, dtype=STATE_REC_DTYPE)
+        p, n = ctypes.c_void_p(), ctypes.c_int64()
+        check(self._lib.hm_top_records(self._ctx, ptr(recs) if recs.size else None, recs.size, HM_MEM_HOST, int(k), HM_MEM_HOST,
+                                       ctypes.byref(p), ctypes.byref(n)), self._ctx, "hm_top_records")
+        return _lib.state_recs_at(p, n.value)
+
+    def window_top(self, k, window_start_us=None, res=None, view=None, copy=True):
+        """The k busiest tiles of one live window (None: the newest) at resolution res <= h3_res (None: h3_res), in rank
+        order: window_records cut to view=(west, south, east, north) when one is given, then the top k by count -- rolled
+        up, filtered, selected and ordered on the GPU in one call (hm_window_top).  A window that is not live gives no
+        record.  copy=False: a view of the library's pinned buffer, valid until the next call on this engine."""
+        res = self.h3_res if res is None else int(res)
+        if window_start_us is None:
+            ws, _ = self.live_windows()
+            window_start_us = ws[-1] if ws.size else 0
+        v = None if view is None else _lib.view_struct(view)
+        p, n = ctypes.c_void_p(), ctypes.c_int64()
+        check(self._lib.hm_window_top(self._ctx, int(window_start_us), res, None if v is None else ctypes.byref(v), int(k),
+                                      HM_MEM_HOST, ctypes.byref(p), ctypes.byref(n)), self._ctx, "hm_window_top")
+        return _lib.state_recs_at(p, n.value, copy)
+
+    def top_info(self):
+        v = (ctypes.c_int64 * 7)()
+        check(self._lib.hm_top_info(self._ctx, v, 7), self._ctx, "hm_top_info")
+        return {"candidates": v[0], "returned": v[1], "count_passes": v[2], "cell_passes": v[3], "index_passes": v[4],
+                "tied": v[5], "device_us": v[6]}
 
     def encode_tile_updates_device(self, city, ttl_minutes):
         """The same, left on the device: (device pointer of the bytes, of the offsets, n statements)."""

@@ -242,12 +242,13 @@ def positions_latest_from_engine(engine, tz=None, view=None):
     return {"type": "FeatureCollection", "features": kept}
 
 
-def tiles_latest_body(engine, res=None, tz=None, view=None):
+def tiles_latest_body(engine, res=None, tz=None, view=None, top=None):
     """The response body of api_tiles_latest as bytes: json.dumps(tiles_latest_from_engine(engine, res, tz=tz),
     separators=(",", ":")), rolled up and encoded on the GPU in one call (HeatmapEngine.window_geojson).  The dict-building
     functions above stay as the comparison form, as stream.tile_ops is for the sink.  view: the tiles in view only,
-    filtered on the GPU."""
-    return engine.window_geojson(None, res, tz, view=view)
+    filtered on the GPU.  top=k: the body of a /api/tiles/top?n=k route -- the k busiest of those tiles in rank order,
+    json.dumps(tiles_top_from_engine(engine, k, res, tz=tz, view=view), separators=(",", ":")), selected on the GPU."""
+    return engine.window_geojson(None, res, tz, view=view, top=top)
 
 
 def positions_latest_body(engine, tz=None, view=None):
@@ -319,13 +320,14 @@ def tiles_latest_png(engine, z, x, y, res=None, size=256):
 
 
 # ---- the positions state as density cells (HeatmapEngine.positions_density, csrc/k_density.h) ----
-def positions_density_from_engine(engine, res=None, since_us=None, tz=None, as_of_us=None, view=None):
+def positions_density_from_engine(engine, res=None, since_us=None, tz=None, as_of_us=None, view=None, top=None):
     """The FeatureCollection a /api/positions/density?res=&since=&bbox= route returns: one tile feature (the shape of
     tiles_latest_collection, so the reference page's tilesLayer colours it by properties.count as it is) per H3 cell of
     resolution res that holds a vehicle of the engine's positions state seen since since_us -- cellId, count,
     avgSpeedKmh 0.0 (positions carry no speed), windowStart = since_us and windowEnd = as_of_us (the caller's "now") as
     tile_docs_from_engine formats a window's bounds, "" for None, and the cell's ring.  view: only the cells whose ring
-    meets it, filtered here in Python (ring_in_view).  The comparison form of positions_density_body."""
+    meets it, filtered here in Python (ring_in_view).  top=k: the k features with the largest count in rank order, taken
+    here in Python after the view (top_of's order).  The comparison form of positions_density_body."""
     recs = engine.positions_density(res, since_us)
     ws, we = _lib.wall_iso(since_us, tz), _lib.wall_iso(as_of_us, tz)
     geoms = rings([int(c) for c in recs["cell"]], engine.device)
@@ -335,13 +337,15 @@ def positions_density_from_engine(engine, res=None, since_us=None, tz=None, as_o
                  "windowEnd": we}
         features.append({"type": "Feature", "geometry": {"type": "Polygon", "coordinates": [ring]}, "properties": props})
     fc = {"type": "FeatureCollection", "features": features}
-    return fc if view is None else _tile_features_in_view(fc, view)
+    fc = fc if view is None else _tile_features_in_view(fc, view)
+    return fc if top is None else _top_features(fc, top)
 
 
-def positions_density_body(engine, res=None, since_us=None, tz=None, as_of_us=None, view=None):
+def positions_density_body(engine, res=None, since_us=None, tz=None, as_of_us=None, view=None, top=None):
     """The same response as bytes: json.dumps(positions_density_from_engine(...), separators=(",", ":")) up to the order of
-    the features, grouped, filtered and encoded on the GPU (HeatmapEngine.positions_density_geojson)."""
-    return engine.positions_density_geojson(res, since_us, tz, as_of_us, view=view)
+    the features, grouped, filtered and encoded on the GPU (HeatmapEngine.positions_density_geojson).  top=k: the k cells
+    with the most vehicles in rank order -- then the bytes are equal including the order of the features."""
+    return engine.positions_density_geojson(res, since_us, tz, as_of_us, view=view, top=top)
 
 
 def positions_density_png(engine, z, x, y, res=None, since_us=None, size=256):
@@ -351,3 +355,39 @@ def positions_density_png(engine, z, x, y, res=None, since_us=None, size=256):
     lat, lon = tile_grid(z, x, y, size)
     _, classes = engine.positions_density_raster(lat, lon, res, since_us, COUNT_THRESHOLDS, copy=False)
     return png_from_classes(classes, COUNT_PALETTE)
+
+
+# ---- top-k hotspots: the k records with the largest count in rank order (HeatmapEngine.top_records, csrc/k_top.h) ----
+TOP_MAX = _lib.HM_TOP_MAX
+
+
+def top_order(count, cell, k):
+    """The input indices of the first min(k, n) records in the top's order: count descending as int64, then cell
+    ascending as uint64, then input index ascending."""
+    count, cell = np.asarray(count).astype(np.int64), np.asarray(cell).astype(np.uint64)
+    k = int(k)
+    if not 0 <= k <= TOP_MAX:
+        raise ValueError(f"k = {k} outside 0..{TOP_MAX}")
+    # (~count is -count - 1: descending count without the overflow of -INT64_MIN)
+    return np.lexsort((np.arange(count.size), cell, ~count))[:k]
+
+
+def top_of(records, k):
+    """top(records, k) in numpy: the first min(k, n) STATE_REC_DTYPE records of the order, whole -- the comparison form of
+    HeatmapEngine.top_records / window_top / positions_density(top=)."""
+    records = np.asarray(records, dtype=_lib.STATE_REC_DTYPE)
+    return records[top_order(records["count"], records["cell"], k)]
+
+
+def _top_features(collection, k):
+    """the k tile features with the largest properties.count, in rank order"""
+    f = collection["features"]
+    order = top_order([x["properties"]["count"] for x in f], [_cell_int(x["properties"]["cellId"]) for x in f], k)
+    return {"type": "FeatureCollection", "features": [f[int(i)] for i in order]}
+
+
+def tiles_top_from_engine(engine, k, res=None, city="boston", tz=None, view=None):
+    """The FeatureCollection a /api/tiles/top?n=k&res=&bbox= route returns: the k busiest tiles of the newest live window
+    at resolution res (in view, when a view is given -- the view comes first), in rank order; tiles_latest_from_engine's
+    features, filtered, ranked and cut here in Python.  The comparison form of tiles_latest_body(top=k)."""
+    return _top_features(tiles_latest_from_engine(engine, res, city, tz, view), k)
