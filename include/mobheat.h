@@ -734,6 +734,81 @@ int hm_selftest_top_records(const hm_state_rec *recs, int64_t n, int64_t k, hm_s
  * the first call. */
 int hm_top_info(const hm_ctx *ctx, int64_t *v, int32_t n);
 
+/* ---- radius queries: the vehicles / tiles nearest a point, nearest first (what the reference's 2dsphere indexes on
+ * positions_latest.loc and tiles.centroid serve: $nearSphere, $geoWithin $centerSphere) ----
+ * Distance of the query point (lat0, lon0) to a candidate (lat, lon), degrees, in binary64, every operation one
+ * rounding in this order, no FMA contraction:
+ *   D   = 0.017453292519943295                      (the double Python's math.radians multiplies by)
+ *   p0  = lat0 * D;  p1 = lat * D
+ *   s_h = sin((p1 - p0) * 0.5);  s_l = sin(((lon - lon0) * D) * 0.5);  c0 = cos(p0);  c1 = cos(p1)
+ *   a   = s_h * s_h + (c0 * c1) * (s_l * s_l)
+ *   r   = sqrt(a);  if (r > 1.0) r = 1.0
+ *   d   = (2.0 * HM_EARTH_RADIUS_M) * asin(r)
+ * sin / cos / asin are glibc's (csrc/glibc_libm.h, the ones latLngToCell and cellToBoundary use), sqrt the correctly
+ * rounded one.  The longitude difference is not normalised: sin^2 of its half is periodic, the antimeridian needs no
+ * case.  +0.0 <= d <= pi R, or NaN when a stored coordinate is not finite (hm_positions_import does not check them): a
+ * NaN candidate is dropped and counted (hm_near_info).  mobheat/readside.py near_distance_m is the same lines in Python;
+ * equality is bit equality of d -- there is no tolerance anywhere.
+ *   filter  a candidate is kept iff d <= max_distance_m, a closed comparison; max_distance_m finite and >= 0, or +inf
+ *           for no limit.  Positions calls also take since_us with hm_positions_density's meaning (kept iff ts_us >=
+ *           since_us; INT64_MIN keeps all).
+ *   order   nearest first; ties by the second key word ascending -- provider code << 32 | vehicle code for positions,
+ *           the cell for tiles --, then by the candidate's input index (decides only among caller records that repeat
+ *           both).  As the top's key: word 0 = the bits of d (non-negative doubles order as unsigned integers).
+ *   k       0..HM_TOP_MAX with the top's rules: outside gives HM_E_INVALID, k == 0 gives HM_OK with *n = 0.
+ *   a tile's point is its centroid as the sink writes it: (sum_lat / count, sum_lon / count) of the rolled-up record,
+ *           one division each, computed before the distance.
+ * Query validation: lat in [-90, 90], lon in [-180, 180], max_distance_m >= 0 or +inf, none NaN; anything else:
+ * HM_E_INVALID, nothing touched.  Outputs are library-owned with buffers of their own, in device or pinned host memory
+ * per out_memory, valid until the next call on the context; the calls read state only (hm_state_version untouched) and
+ * a repeated call of the same size allocates nothing. */
+#define HM_EARTH_RADIUS_M 6378100.0   /* MongoDB's sphere */
+typedef struct { double lat, lon, max_distance_m; } hm_near;
+/* dist_m[i] = d(q, (lat[i], lon[i])) on GPU `device`; memory / device as hm_cells_to_boundary (with HM_MEM_DEVICE lat,
+ * lon and dist_m are device pointers).  max_distance_m is validated, not applied. */
+int hm_near_distances(const hm_near *q, const double *lat, const double *lon, int64_t n, int32_t memory, int32_t device,
+                      double *dist_m);
+/* Host execution of the same code (no GPU). */
+int hm_selftest_near_distances(const hm_near *q, const double *lat, const double *lon, int64_t n, double *dist_m);
+/* The k nearest of the positions state S within the radius: *n records in rank order and their distances.  State
+ * errors as hm_positions_density's (a shard context: HM_E_UNSUPPORTED; between stage calls: HM_E_STATE); an empty S:
+ * *n = 0. */
+int hm_positions_near(hm_ctx *ctx, const hm_near *q, int64_t since_us, int64_t k, int32_t out_memory,
+                      const hm_position_rec **recs, const double **dist_m, int64_t *n);
+/* The k tiles of hm_window_rollup(window_start_us, res) whose centroid is nearest within the radius.  hm_window_top's
+ * rules: a window that is not live: *n = 0; a shard context: HM_E_UNSUPPORTED (a parent split over ranks has no
+ * rank-local centroid); between stage calls: HM_E_STATE. */
+int hm_window_near(hm_ctx *ctx, int64_t window_start_us, int32_t res, const hm_near *q, int64_t k, int32_t out_memory,
+                   const hm_state_rec **recs, const double **dist_m, int64_t *n);
+/* hm_positions_near, then the ranked records' features in rank order by hm_positions_geojson's encoder with
+ * ,"distanceM":<repr of d> appended as the last property, the records never leaving the device: body, offsets and *n as
+ * hm_positions_geojson's (none returned: the 42-byte empty body); recs / dist_m (optional): the records in feature order
+ * and their distances, pinned host memory.  Errors as hm_positions_near's and hm_positions_geojson's. */
+int hm_positions_geojson_near(hm_ctx *ctx, const hm_position_doc_cfg *buckets, const hm_near *q, int64_t since_us, int64_t k,
+                              int32_t out_memory, const uint8_t **bytes, const int64_t **offsets, int64_t *n,
+                              const hm_position_rec **recs, const double **dist_m);
+/* hm_window_near, then the tile features in rank order with distanceM as their last property; as hm_window_geojson_top. */
+int hm_window_geojson_near(hm_ctx *ctx, int64_t window_start_us, int32_t res, const hm_geojson_cfg *cfg, const hm_near *q,
+                           int64_t k, int32_t out_memory, const uint8_t **bytes, const int64_t **offsets, int64_t *n,
+                           const hm_state_rec **recs, const double **dist_m);
+/* hm_selftest_tile_features / hm_selftest_position_features with an optional distance per record (dist_m NULL: the
+ * bytes of those calls): host execution of the encoders the near bodies use. */
+int hm_selftest_tile_features_near(const hm_geojson_cfg *cfg, const hm_state_rec *recs, int64_t n, const double *dist_m,
+                                   uint8_t *bytes, int64_t cap, int64_t *offsets);
+int hm_selftest_position_features_near(const hm_position_doc_cfg *cfg, const hm_position_rec *recs, int64_t n,
+                                       const double *dist_m, uint8_t *bytes, int64_t cap, int64_t *offsets);
+/* Host execution of the filter, the keys, the select and the ordering with the kernels' own code on caller records (no
+ * GPU): out / dist_m have room for min(k, n), *n_out = the records returned. */
+int hm_selftest_positions_near(const hm_near *q, int64_t since_us, const hm_position_rec *recs, int64_t n, int64_t k,
+                               hm_position_rec *out, double *dist_m, int64_t *n_out);
+int hm_selftest_tiles_near(const hm_near *q, const hm_state_rec *recs, int64_t n, int64_t k, hm_state_rec *out,
+                           double *dist_m, int64_t *n_out);
+/* up to n of, for the last near call on the context: [0] pair-table slots / roll-up records scanned, [1] kept by since_us,
+ * [2] dropped as NaN, [3] within the radius (the select's candidates), [4] returned, [5] select passes, [6] device
+ * microseconds of the emit kernel, [7] of the select and the scatter (HIP events, as the top's).  All 0 before the first
+ * call. */
+int hm_near_info(const hm_ctx *ctx, int64_t *v, int32_t n);
+
 /* json.dumps(x) of n doubles -- CPython's float.__repr__, NaN / Infinity / -Infinity for the non-finite -- as the GeoJSON
  * encoders write them (csrc/float_repr.h), executed on the host and on GPU `device` (test entry points): value i's
  * len[i] <= 24 bytes at text[24 i]. */

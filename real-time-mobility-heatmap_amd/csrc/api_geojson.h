@@ -85,9 +85,10 @@ static int gj_out(hm_ctx *ctx, int64_t n, int64_t body_len, int32_t out_memory, 
     return HM_OK;
 }
 
-// the features of n device records: sizes -> scan -> write -> out
+// the features of n device records: sizes -> scan -> write -> out.  dist_m (optional, device): a distance per record
+// for the near bodies' distanceM
 static int gj_tiles(hm_ctx *ctx, const GjTexts &T, const GrowRec *recs, int64_t n, int32_t out_memory, const uint8_t **bytes,
-                    const int64_t **offsets) {
+                    const int64_t **offsets, const double *dist_m = nullptr) {
     hm_ctx::GeoJson &G = ctx->gj;
     int rc;
     if ((rc = gj_init(ctx))) return rc;
@@ -101,7 +102,7 @@ static int gj_tiles(hm_ctx *ctx, const GjTexts &T, const GrowRec *recs, int64_t 
     HIPCHK(ctx, hipMemsetAsync(words, 0, GJW_WORDS * 8, ctx->stream));
     HIPCHK(ctx, hipEventRecord(G.ev[0], ctx->stream));
     hipLaunchKernelGGL(k_gj_tile_sizes, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, T, recs, n, vlat, vlng, (int *)G.vn.p,
-                       (unsigned *)G.sizes.p, words);
+                       (unsigned *)G.sizes.p, words, dist_m);
     HIPCHK(ctx, hipEventRecord(G.ev[1], ctx->stream));
     gj_scan(ctx, n);
     HIPCHK(ctx, hipGetLastError());
@@ -109,15 +110,16 @@ static int gj_tiles(hm_ctx *ctx, const GjTexts &T, const GrowRec *recs, int64_t 
     HIPCHK(ctx, hipMemcpyAsync(&total, (unsigned long long *)G.off.p + n + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(&longest, words + GJW_MAX, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, ctx_sync(ctx, __LINE__));
-    if (longest == 0 || longest > (unsigned long long)GJ_TILE_MAX)
-        return set_err(ctx, HM_E_STATE, "a tile feature of %llu bytes (at most %d expected)", longest, GJ_TILE_MAX);
+    const int tile_max = GJ_TILE_MAX + (dist_m ? GJ_DIST_MAX : 0);
+    if (longest == 0 || longest > (unsigned long long)tile_max)
+        return set_err(ctx, HM_E_STATE, "a tile feature of %llu bytes (at most %d expected)", longest, tile_max);
     const int64_t body_len = (int64_t)total + 1;
     if ((rc = ensure(ctx, G.bytes, (size_t)body_len + 16))) return rc;
-    const size_t lds = (size_t)GJ_THREADS * ((longest + 15) & ~15ull) + 64;   // (<= 64 x 880 + 64 B: below the 64-KB default)
+    const size_t lds = (size_t)GJ_THREADS * ((longest + 15) & ~15ull) + 64;   // (<= 64 x 912 + 64 B: below the 64-KB default)
     HIPCHK(ctx, hipEventRecord(G.ev[2], ctx->stream));
     hipLaunchKernelGGL(k_gj_tile_write, dim3(grid_for(n, GJ_THREADS)), dim3(GJ_THREADS), lds, ctx->stream, T, recs, n,
                        (const double *)vlat, (const double *)vlng, (const int *)G.vn.p, (const unsigned long long *)G.off.p,
-                       (uint8_t *)G.bytes.p);
+                       (uint8_t *)G.bytes.p, dist_m);
     HIPCHK(ctx, hipEventRecord(G.ev[3], ctx->stream));
     HIPCHK(ctx, hipGetLastError());
     return gj_out(ctx, n, body_len, out_memory, bytes, offsets);
@@ -164,8 +166,8 @@ int hm_window_geojson(hm_ctx *ctx, int64_t window_start_us, int32_t res, const h
     return HM_OK;
 }
 
-int hm_selftest_tile_features(const hm_geojson_cfg *cfg, const hm_state_rec *recs, int64_t n, uint8_t *bytes, int64_t cap,
-                              int64_t *offsets) {
+int hm_selftest_tile_features_near(const hm_geojson_cfg *cfg, const hm_state_rec *recs, int64_t n, const double *dist_m,
+                                   uint8_t *bytes, int64_t cap, int64_t *offsets) {
     GjTexts T;
     if (n < 0 || !bytes || !offsets || (n > 0 && !recs) || cap < (int64_t)sizeof(GJ_EMPTY_BODY) - 1) return HM_E_INVALID;
     if (gj_texts(cfg, T)) return HM_E_INVALID;
@@ -176,9 +178,10 @@ int hm_selftest_tile_features(const hm_geojson_cfg *cfg, const hm_state_rec *rec
         offsets[i] = o;
         double la[10], lo[10];
         const int nv = cellToBoundaryDeg(recs[i].cell, H, la, lo);
-        const int len = tile_feature(nullptr, T, recs[i].cell, recs[i].count, recs[i].n_speed, recs[i].sum_speed, nv, la, lo, 1);
+        const double *d = dist_m ? dist_m + i : nullptr;
+        const int len = tile_feature(nullptr, T, recs[i].cell, recs[i].count, recs[i].n_speed, recs[i].sum_speed, nv, la, lo, 1, d);
         if (o + len + 2 > cap) return HM_E_INVALID;
-        tile_feature(bytes + o, T, recs[i].cell, recs[i].count, recs[i].n_speed, recs[i].sum_speed, nv, la, lo, 1);
+        tile_feature(bytes + o, T, recs[i].cell, recs[i].count, recs[i].n_speed, recs[i].sum_speed, nv, la, lo, 1, d);
         o += len;
         bytes[o++] = i == n - 1 ? ']' : ',';
     }
@@ -186,6 +189,11 @@ int hm_selftest_tile_features(const hm_geojson_cfg *cfg, const hm_state_rec *rec
     if (n == 0) bytes[o++] = ']';
     bytes[o] = '}';
     return HM_OK;
+}
+
+int hm_selftest_tile_features(const hm_geojson_cfg *cfg, const hm_state_rec *recs, int64_t n, uint8_t *bytes, int64_t cap,
+                              int64_t *offsets) {
+    return hm_selftest_tile_features_near(cfg, recs, n, nullptr, bytes, cap, offsets);
 }
 
 // ---- positions ----
@@ -229,9 +237,17 @@ int hm_positions_buckets(hm_ctx *ctx, int64_t *bucket_ids, int64_t cap, int64_t 
     return HM_OK;
 }
 
-// hm_positions_geojson (view nullptr: the whole state) and hm_positions_geojson_view (api_view.h: the valid view's part)
+// device records to encode instead of the state's own emission, in feature order, with a distance each (the near body)
+struct GjGiven {
+    const hm_position_rec *recs;
+    const double *dist_m;
+    int64_t n;
+};
+// hm_positions_geojson (view nullptr: the whole state), hm_positions_geojson_view (api_view.h: the valid view's part) and
+// hm_positions_geojson_near (api_near.h: `given`, the ranked records)
 static int gj_positions(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t out_memory, const uint8_t **bytes,
-                        const int64_t **offsets, int64_t *n, const hm_position_rec **recs, const hm_view *view, const char *who) {
+                        const int64_t **offsets, int64_t *n, const hm_position_rec **recs, const hm_view *view, const char *who,
+                        const GjGiven *given = nullptr) {
     if (!ctx || !buckets || !bytes || !offsets || !n || (out_memory != HM_MEM_HOST && out_memory != HM_MEM_DEVICE))
         return ctx ? set_err(ctx, HM_E_INVALID, "bad argument") : HM_E_INVALID;
     if (ctx->shard_count > 1)
@@ -246,7 +262,8 @@ static int gj_positions(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t
     if (recs) *recs = nullptr;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if ((rc = gj_init(ctx))) return rc;
-    int64_t m = P.tab ? P.keys : 0;
+    int64_t m = given ? given->n : P.tab ? P.keys : 0;
+    const double *dist_m = given ? given->dist_m : nullptr;
     if (view) {
         G.candidates = m;
         G.view_us = 0;
@@ -256,7 +273,7 @@ static int gj_positions(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t
         return gj_out(ctx, 0, (int64_t)sizeof(GJ_EMPTY_BODY) - 1, out_memory, bytes, offsets);
     }
     const int64_t nb = buckets->n_buckets;
-    if ((rc = gj_scan_buffers(ctx, m)) || (rc = ensure(ctx, G.precs, (size_t)m * sizeof(hm_position_rec))) ||
+    if ((rc = gj_scan_buffers(ctx, m)) || (!given && (rc = ensure(ctx, G.precs, (size_t)m * sizeof(hm_position_rec)))) ||
         (rc = ensure(ctx, G.params, (size_t)std::max<int64_t>(nb, 1) * 16)))
         return rc;
     unsigned long long *words = (unsigned long long *)G.words.p;
@@ -266,7 +283,8 @@ static int gj_positions(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t
         HIPCHK(ctx, hipMemcpyAsync((int64_t *)G.params.p + nb, buckets->bucket_offset_s, (size_t)nb * 8, hipMemcpyHostToDevice, ctx->stream));
     }
     // the state's records in feature order (k_pos_emit's compaction, into a buffer of this call's own)
-    if (!view) {
+    if (given) {   // (nothing to emit: the caller's records)
+    } else if (!view) {
         hipLaunchKernelGGL(k_pos_emit, dim3(grid_for((int64_t)P.cap, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, (const PosSlot *)P.tab,
                            (int64_t)P.cap, (hm_position_rec *)G.precs.p, m, words + GJW_OUT);
     } else {   // the same compaction with the point test; the features run over what it kept
@@ -299,9 +317,9 @@ static int gj_positions(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t
     F.n_buckets = nb;
     F.bucket_id = (const int64_t *)G.params.p;
     F.bucket_off = F.bucket_id + nb;
-    const hm_position_rec *d = (const hm_position_rec *)G.precs.p;
+    const hm_position_rec *d = given ? given->recs : (const hm_position_rec *)G.precs.p;
     HIPCHK(ctx, hipEventRecord(G.ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_gj_pos_sizes, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, F, d, m, (unsigned *)G.sizes.p, words);
+    hipLaunchKernelGGL(k_gj_pos_sizes, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, F, d, m, (unsigned *)G.sizes.p, words, dist_m);
     HIPCHK(ctx, hipEventRecord(G.ev[1], ctx->stream));
     gj_scan(ctx, m);
     HIPCHK(ctx, hipGetLastError());
@@ -309,7 +327,7 @@ static int gj_positions(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t
     HIPCHK(ctx, hipMemcpyAsync(&total, (unsigned long long *)G.off.p + m + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(hw, words, GJW_WORDS * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, ctx_sync(ctx, __LINE__));   // (the bucket table is pageable host memory)
-    if ((int64_t)hw[GJW_OUT] != m) return set_err(ctx, HM_E_STATE, "positions state holds %llu keys, %lld expected", hw[GJW_OUT], (long long)m);
+    if (!given && (int64_t)hw[GJW_OUT] != m) return set_err(ctx, HM_E_STATE, "positions state holds %llu keys, %lld expected", hw[GJW_OUT], (long long)m);
     if (hw[GJW_BAD])
         return set_err(ctx, HM_E_INVALID, "%llu positions outside the time buckets or years 1-9999, or with a string that is not UTF-8",
                        hw[GJW_BAD]);
@@ -317,12 +335,12 @@ static int gj_positions(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t
     if ((rc = ensure(ctx, G.bytes, (size_t)body_len + 16))) return rc;
     HIPCHK(ctx, hipEventRecord(G.ev[2], ctx->stream));
     hipLaunchKernelGGL(k_gj_pos_write, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, F, d, m, (const unsigned long long *)G.off.p,
-                       (uint8_t *)G.bytes.p);
+                       (uint8_t *)G.bytes.p, dist_m);
     HIPCHK(ctx, hipEventRecord(G.ev[3], ctx->stream));
     HIPCHK(ctx, hipGetLastError());
     if (recs) {
         if ((rc = host_pinned(ctx, &G.h_recs, G.h_recs_cap, (size_t)m * sizeof(hm_position_rec)))) return rc;
-        HIPCHK(ctx, hipMemcpyAsync(G.h_recs, G.precs.p, (size_t)m * sizeof(hm_position_rec), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(G.h_recs, d, (size_t)m * sizeof(hm_position_rec), hipMemcpyDeviceToHost, ctx->stream));
         *recs = (const hm_position_rec *)G.h_recs;
     }
     if ((rc = gj_out(ctx, m, body_len, out_memory, bytes, offsets))) return rc;
@@ -335,8 +353,8 @@ int hm_positions_geojson(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_
     return gj_positions(ctx, buckets, out_memory, bytes, offsets, n, recs, nullptr, "hm_positions_geojson");
 }
 
-int hm_selftest_position_features(const hm_position_doc_cfg *cfg, const hm_position_rec *recs, int64_t n, uint8_t *bytes,
-                                  int64_t cap, int64_t *offsets) {
+int hm_selftest_position_features_near(const hm_position_doc_cfg *cfg, const hm_position_rec *recs, int64_t n, const double *dist_m,
+                                       uint8_t *bytes, int64_t cap, int64_t *offsets) {
     if (!cfg || n < 0 || !bytes || !offsets || (n > 0 && !recs) || cap < (int64_t)sizeof(GJ_EMPTY_BODY) - 1) return HM_E_INVALID;
     if (cfg->n_providers < 0 || cfg->n_vehicles < 0 || cfg->n_buckets < 0 || (cfg->n_providers && (!cfg->provider_offsets || !cfg->provider_bytes)) ||
         (cfg->n_vehicles && (!cfg->vehicle_offsets || !cfg->vehicle_bytes)) || (cfg->n_buckets && (!cfg->bucket_ids || !cfg->bucket_offset_s)))
@@ -354,9 +372,10 @@ int hm_selftest_position_features(const hm_position_doc_cfg *cfg, const hm_posit
         const uint8_t *vs = (const uint8_t *)cfg->vehicle_bytes + cfg->vehicle_offsets[r.vehicle];
         const int pl = (int)(cfg->provider_offsets[r.provider + 1] - cfg->provider_offsets[r.provider]);
         const int vl = (int)(cfg->vehicle_offsets[r.vehicle + 1] - cfg->vehicle_offsets[r.vehicle]);
-        const int len = position_feature(nullptr, ps, pl, vs, vl, r.ts_us, off_s, r.lat, r.lon);
+        const double *d = dist_m ? dist_m + i : nullptr;
+        const int len = position_feature(nullptr, ps, pl, vs, vl, r.ts_us, off_s, r.lat, r.lon, d);
         if (len < 0 || o + len + 2 > cap) return HM_E_INVALID;
-        position_feature(bytes + o, ps, pl, vs, vl, r.ts_us, off_s, r.lat, r.lon);
+        position_feature(bytes + o, ps, pl, vs, vl, r.ts_us, off_s, r.lat, r.lon, d);
         o += len;
         bytes[o++] = i == n - 1 ? ']' : ',';
     }
@@ -364,6 +383,11 @@ int hm_selftest_position_features(const hm_position_doc_cfg *cfg, const hm_posit
     if (n == 0) bytes[o++] = ']';
     bytes[o] = '}';
     return HM_OK;
+}
+
+int hm_selftest_position_features(const hm_position_doc_cfg *cfg, const hm_position_rec *recs, int64_t n, uint8_t *bytes,
+                                  int64_t cap, int64_t *offsets) {
+    return hm_selftest_position_features_near(cfg, recs, n, nullptr, bytes, cap, offsets);
 }
 
 int hm_geojson_info(const hm_ctx *ctx, int64_t *v, int32_t n) {

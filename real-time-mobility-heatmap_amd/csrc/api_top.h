@@ -45,6 +45,101 @@ struct TopSegment {
     }
 };
 
+// The select and the ordering on two device arrays of key words (kc[n], cell[n]; word 2 is the index), a step of
+// top_run, which is how callers reach it: the control block is uploaded (top_control), the OR / NAND of both words
+// reduced into it inside the open segment and that segment ended.  Leaves the m selected candidates' indices in T.sidx and their ranks in T.rank, with the last
+// segment open: the caller launches its scatter and calls top_finish.  passes[3]: the passes per key word; *tied: the
+// candidates still tied with the threshold when the walk stopped.
+static int top_select(hm_ctx *ctx, const unsigned long long *kc, const unsigned long long *cell, int64_t n, int64_t m,
+                      TopSegment &seg, double &us, int64_t *passes, int64_t *tied) {
+    hm_ctx::Top &T = ctx->top;
+    unsigned long long *words = (unsigned long long *)T.words.p;
+    const int max_grid = T.test_grid ? T.test_grid : 8 * std::max(ctx->n_cus, 1);
+    const int stream_grid = grid_for(n, 256, max_grid);
+    unsigned long long w[4] = {};
+    HIPCHK(ctx, hipMemcpyAsync(w, words + TW_OR_C, 32, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, ctx_sync(ctx, __LINE__));
+    seg.add(us);
+    TopPass plan[20];
+    const int np = top_plan(w[0] ^ ~w[1], w[2] ^ ~w[3], n, plan);
+    TopMasks M = {0, 0, 0};
+    unsigned long long nt[2] = {(unsigned long long)m, (unsigned long long)n};   // need, tied
+    for (int p = 0; p < np && nt[1] != nt[0]; p++) {
+        HIPCHK(ctx, seg.begin());
+        hipLaunchKernelGGL(k_top_hist, dim3(stream_grid), dim3(256), 0, ctx->stream, kc, cell, n, M, plan[p].word, plan[p].shift, words);
+        hipLaunchKernelGGL(k_top_pick, dim3(1), dim3(64), 0, ctx->stream, words, plan[p].word, plan[p].shift);
+        HIPCHK(ctx, seg.end());
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(nt, words + TW_NEED, 16, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(ctx, ctx_sync(ctx, __LINE__));
+        seg.add(us);
+        top_examine(M, plan[p]);
+        passes[plan[p].word]++;
+        if (nt[0] < 1 || nt[0] > nt[1] || nt[1] > (unsigned long long)n)
+            return set_err(ctx, HM_E_STATE, "top select: %llu needed of %llu tied after pass %d", nt[0], nt[1], p);
+    }
+    if (nt[1] != nt[0]) return set_err(ctx, HM_E_STATE, "top select: %llu needed of %llu tied with no byte left", nt[0], nt[1]);
+    *tied = (int64_t)nt[1];
+    // the selected and their ranks
+    const int jblocks = (int)((m + 255) / 256);
+    const int splits = std::max(1, std::min(jblocks, 4 * std::max(ctx->n_cus, 1) / jblocks));
+    HIPCHK(ctx, seg.begin());
+    hipLaunchKernelGGL(k_top_compact, dim3(grid_for(n, 256 * DUMP_PER, max_grid)), dim3(256), 0, ctx->stream, kc, cell, n, M, words,
+                       (unsigned long long *)T.skc.p, (unsigned long long *)T.scell.p, (unsigned *)T.sidx.p, (unsigned long long)m);
+    HIPCHK(ctx, hipMemsetAsync(T.rank.p, 0, (size_t)m * 4, ctx->stream));
+    hipLaunchKernelGGL(k_top_rank, dim3(jblocks, splits), dim3(256), 0, ctx->stream, (const unsigned long long *)T.skc.p,
+                       (const unsigned long long *)T.scell.p, (const unsigned *)T.sidx.p, (int)m, (unsigned *)T.rank.p);
+    return HM_OK;
+}
+// the select's buffers for m selected of any number of candidates
+static int top_select_buffers(hm_ctx *ctx, int64_t m) {
+    hm_ctx::Top &T = ctx->top;
+    int rc;
+    if ((rc = ensure(ctx, T.skc, (size_t)m * 8)) || (rc = ensure(ctx, T.scell, (size_t)m * 8)) || (rc = ensure(ctx, T.sidx, (size_t)m * 4)) ||
+        (rc = ensure(ctx, T.rank, (size_t)m * 4)))
+        return rc;
+    return HM_OK;
+}
+// the control block: everything 0 but the need and the tied group, which is every candidate
+static hipError_t top_control(hm_ctx *ctx, int64_t n, int64_t m) {
+    hm_ctx::Top &T = ctx->top;
+    memset(T.h_words, 0, sizeof T.h_words);
+    T.h_words[TW_NEED] = (unsigned long long)m;
+    T.h_words[TW_TIED] = (unsigned long long)n;
+    return hipMemcpyAsync(T.words.p, T.h_words, TW_WORDS * 8, hipMemcpyHostToDevice, ctx->stream);
+}
+// after the caller's scatter: the last segment's end, and k_top_compact's count against m
+static int top_finish(hm_ctx *ctx, TopSegment &seg, double &us, int64_t m) {
+    HIPCHK(ctx, seg.end());
+    HIPCHK(ctx, hipGetLastError());
+    unsigned long long got = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&got, (unsigned long long *)ctx->top.words.p + TW_OUT, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, ctx_sync(ctx, __LINE__));
+    seg.add(us);
+    if ((int64_t)got != m) return set_err(ctx, HM_E_STATE, "top select kept %llu records, %lld expected", got, (long long)m);
+    return HM_OK;
+}
+// The whole protocol in one place: the control block, `vary` (launches the kernel that reduces the OR / NAND of the key
+// words into the control block -- k_top_keys while it extracts the keys, k_near_vary over keys that exist), the select
+// and the ranks (top_select), `scatter` (launches the caller's kernel that copies its records by T.sidx / T.rank), and
+// the final count (top_finish).  us gains the device time of all of it.
+extern "C++" {
+template <class Vary, class Scatter>
+static int top_run(hm_ctx *ctx, const unsigned long long *kc, const unsigned long long *cell, int64_t n, int64_t m, double &us,
+                   int64_t *passes, int64_t *tied, Vary vary, Scatter scatter) {
+    TopSegment seg(ctx);
+    HIPCHK(ctx, top_control(ctx, n, m));
+    HIPCHK(ctx, seg.begin());
+    vary();
+    HIPCHK(ctx, seg.end());
+    HIPCHK(ctx, hipGetLastError());
+    int rc;
+    if ((rc = top_select(ctx, kc, cell, n, m, seg, us, passes, tied))) return rc;
+    scatter();
+    return top_finish(ctx, seg, us, m);
+}
+}  // extern "C++"
+
 // top(recs[0, n), k) on the device: *out = the first min(k, n) records of the order in T.out (device), *m_out their
 // number.  recs: device memory, 16-byte aligned.  Fills T.info; reads recs only.
 static int top_on_device(hm_ctx *ctx, const GrowRec *recs, int64_t n, int64_t k, const GrowRec **out, int64_t *m_out) {
@@ -58,68 +153,20 @@ static int top_on_device(hm_ctx *ctx, const GrowRec *recs, int64_t n, int64_t k,
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc;
     if ((rc = top_init(ctx)) || (rc = ensure(ctx, T.kc, (size_t)n * 8)) || (rc = ensure(ctx, T.cell, (size_t)n * 8)) ||
-        (rc = ensure(ctx, T.skc, (size_t)m * 8)) || (rc = ensure(ctx, T.scell, (size_t)m * 8)) || (rc = ensure(ctx, T.sidx, (size_t)m * 4)) ||
-        (rc = ensure(ctx, T.rank, (size_t)m * 4)) || (rc = ensure(ctx, T.out, (size_t)m * sizeof(GrowRec))))
+        (rc = top_select_buffers(ctx, m)) || (rc = ensure(ctx, T.out, (size_t)m * sizeof(GrowRec))))
         return rc;
     unsigned long long *words = (unsigned long long *)T.words.p;
     unsigned long long *kc = (unsigned long long *)T.kc.p, *cell = (unsigned long long *)T.cell.p;
     const int max_grid = T.test_grid ? T.test_grid : 8 * std::max(ctx->n_cus, 1);
-    const int stream_grid = grid_for(n, 256, max_grid);
     double us = 0;
-    TopSegment seg(ctx);
-    // the control block: everything 0 but the need and the tied group, which is every candidate
-    memset(T.h_words, 0, sizeof T.h_words);
-    T.h_words[TW_NEED] = (unsigned long long)m;
-    T.h_words[TW_TIED] = (unsigned long long)n;
-    HIPCHK(ctx, hipMemcpyAsync(words, T.h_words, TW_WORDS * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(ctx, seg.begin());
-    hipLaunchKernelGGL(k_top_keys, dim3(stream_grid), dim3(256), 0, ctx->stream, recs, n, kc, cell, words);
-    HIPCHK(ctx, seg.end());
-    HIPCHK(ctx, hipGetLastError());
-    unsigned long long w[4] = {};
-    HIPCHK(ctx, hipMemcpyAsync(w, words + TW_OR_C, 32, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, ctx_sync(ctx, __LINE__));
-    seg.add(us);
-    TopPass plan[20];
-    const int np = top_plan(w[0] ^ ~w[1], w[2] ^ ~w[3], n, plan);
-    TopMasks M = {0, 0, 0};
-    unsigned long long nt[2] = {(unsigned long long)m, (unsigned long long)n};   // need, tied
-    for (int p = 0; p < np && nt[1] != nt[0]; p++) {
-        HIPCHK(ctx, seg.begin());
-        hipLaunchKernelGGL(k_top_hist, dim3(stream_grid), dim3(256), 0, ctx->stream, (const unsigned long long *)kc,
-                           (const unsigned long long *)cell, n, M, plan[p].word, plan[p].shift, words);
-        hipLaunchKernelGGL(k_top_pick, dim3(1), dim3(64), 0, ctx->stream, words, plan[p].word, plan[p].shift);
-        HIPCHK(ctx, seg.end());
-        HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(nt, words + TW_NEED, 16, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(ctx, ctx_sync(ctx, __LINE__));
-        seg.add(us);
-        top_examine(M, plan[p]);
-        T.info[2 + plan[p].word]++;
-        if (nt[0] < 1 || nt[0] > nt[1] || nt[1] > (unsigned long long)n)
-            return set_err(ctx, HM_E_STATE, "top select: %llu needed of %llu tied after pass %d", nt[0], nt[1], p);
-    }
-    if (nt[1] != nt[0]) return set_err(ctx, HM_E_STATE, "top select: %llu needed of %llu tied with no byte left", nt[0], nt[1]);
-    T.info[5] = (int64_t)nt[1];
-    // the selected, their ranks, the records in rank order
-    const int jblocks = (int)((m + 255) / 256);
-    const int splits = std::max(1, std::min(jblocks, 4 * std::max(ctx->n_cus, 1) / jblocks));
-    HIPCHK(ctx, seg.begin());
-    hipLaunchKernelGGL(k_top_compact, dim3(grid_for(n, 256 * DUMP_PER, max_grid)), dim3(256), 0, ctx->stream,
-                       (const unsigned long long *)kc, (const unsigned long long *)cell, n, M, words, (unsigned long long *)T.skc.p, (unsigned long long *)T.scell.p,
-                       (unsigned *)T.sidx.p, (unsigned long long)m);
-    HIPCHK(ctx, hipMemsetAsync(T.rank.p, 0, (size_t)m * 4, ctx->stream));
-    hipLaunchKernelGGL(k_top_rank, dim3(jblocks, splits), dim3(256), 0, ctx->stream, (const unsigned long long *)T.skc.p,
-                       (const unsigned long long *)T.scell.p, (const unsigned *)T.sidx.p, (int)m, (unsigned *)T.rank.p);
-    hipLaunchKernelGGL(k_top_scatter, dim3(grid_for(4 * m, 256)), dim3(256), 0, ctx->stream, (const uint4 *)recs, n,
-                       (const unsigned *)T.sidx.p, (const unsigned *)T.rank.p, (int)m, (uint4 *)T.out.p);
-    HIPCHK(ctx, seg.end());
-    HIPCHK(ctx, hipGetLastError());
-    unsigned long long got = 0;
-    HIPCHK(ctx, hipMemcpyAsync(&got, words + TW_OUT, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, ctx_sync(ctx, __LINE__));
-    seg.add(us);
-    if ((int64_t)got != m) return set_err(ctx, HM_E_STATE, "top select kept %llu records, %lld expected", got, (long long)m);
+    rc = top_run(
+        ctx, kc, cell, n, m, us, &T.info[2], &T.info[5],
+        [&] { hipLaunchKernelGGL(k_top_keys, dim3(grid_for(n, 256, max_grid)), dim3(256), 0, ctx->stream, recs, n, kc, cell, words); },
+        [&] {   // the records in rank order
+            hipLaunchKernelGGL(k_top_scatter, dim3(grid_for(4 * m, 256)), dim3(256), 0, ctx->stream, (const uint4 *)recs, n,
+                               (const unsigned *)T.sidx.p, (const unsigned *)T.rank.p, (int)m, (uint4 *)T.out.p);
+        });
+    if (rc) return rc;
     T.info[1] = m;
     T.info[6] = (int64_t)us;
     *out = (const GrowRec *)T.out.p;
@@ -274,23 +321,16 @@ int hm_positions_density_top(hm_ctx *ctx, int32_t res, int64_t since_us, const h
     return HM_OK;
 }
 
-// Host execution of the select and the ordering with the kernels' HM_HD helpers: the keys (top_key_count), the plan
-// of varying bytes, the passes' digits (top_digit, top_tied), the selection (top_selected), and the order by the
-// comparator the counting uses (top_before).
-int hm_selftest_top_records(const hm_state_rec *recs, int64_t n, int64_t k, hm_state_rec *out, int64_t *n_out) {
-    if (n < 0 || n > (int64_t(1) << 31) || (n > 0 && !recs) || !top_k_ok(k) || !n_out) return HM_E_INVALID;
-    const int64_t m = std::min(k, n);
-    if (m > 0 && !out) return HM_E_INVALID;
-    *n_out = 0;
-    if (m == 0) return HM_OK;
-    std::vector<unsigned long long> kc((size_t)n);
+// Host execution of the select and the ordering with the kernels' HM_HD helpers on n keys of two words (word 2 is the
+// index): the plan of varying bytes, the passes' digits (top_digit, top_tied), the selection (top_selected), and the
+// order by the comparator the counting uses (top_before).  sel = the m selected indices in rank order.
+static int top_select_host(const unsigned long long *kc, const unsigned long long *cell, int64_t n, int64_t m, std::vector<unsigned> &sel) {
     unsigned long long orc = 0, andc = ~0ull, orl = 0, andl = ~0ull;
     for (int64_t i = 0; i < n; i++) {
-        kc[i] = top_key_count(recs[i].count);
         orc |= kc[i];
         andc &= kc[i];
-        orl |= recs[i].cell;
-        andl &= recs[i].cell;
+        orl |= cell[i];
+        andl &= cell[i];
     }
     TopPass plan[20];
     const int np = top_plan(orc ^ andc, orl ^ andl, n, plan);
@@ -299,8 +339,8 @@ int hm_selftest_top_records(const hm_state_rec *recs, int64_t n, int64_t k, hm_s
     for (int p = 0; p < np && tied != need; p++) {
         unsigned long long h[256] = {};
         for (int64_t i = 0; i < n; i++)
-            if (top_tied(kc[i], recs[i].cell, (unsigned)i, M, prefix[0], prefix[1], (unsigned)prefix[2])) {
-                const unsigned long long word = plan[p].word == 0 ? kc[i] : plan[p].word == 1 ? recs[i].cell : (unsigned long long)(unsigned)i;
+            if (top_tied(kc[i], cell[i], (unsigned)i, M, prefix[0], prefix[1], (unsigned)prefix[2])) {
+                const unsigned long long word = plan[p].word == 0 ? kc[i] : plan[p].word == 1 ? cell[i] : (unsigned long long)(unsigned)i;
                 h[top_digit(word, plan[p].shift)]++;
             }
         unsigned d = 0;
@@ -310,12 +350,29 @@ int hm_selftest_top_records(const hm_state_rec *recs, int64_t n, int64_t k, hm_s
         top_examine(M, plan[p]);
     }
     if (tied != need) return HM_E_STATE;
-    std::vector<unsigned> sel;
+    sel.clear();
     sel.reserve((size_t)m);
     for (int64_t i = 0; i < n; i++)
-        if (top_selected(kc[i], recs[i].cell, (unsigned)i, M, prefix[0], prefix[1], (unsigned)prefix[2])) sel.push_back((unsigned)i);
+        if (top_selected(kc[i], cell[i], (unsigned)i, M, prefix[0], prefix[1], (unsigned)prefix[2])) sel.push_back((unsigned)i);
     if ((int64_t)sel.size() != m) return HM_E_STATE;
-    std::sort(sel.begin(), sel.end(), [&](unsigned a, unsigned b) { return top_before(kc[a], recs[a].cell, a, kc[b], recs[b].cell, b); });
+    std::sort(sel.begin(), sel.end(), [&](unsigned a, unsigned b) { return top_before(kc[a], cell[a], a, kc[b], cell[b], b); });
+    return HM_OK;
+}
+
+// Host execution of the top: the keys (top_key_count), then top_select_host.
+int hm_selftest_top_records(const hm_state_rec *recs, int64_t n, int64_t k, hm_state_rec *out, int64_t *n_out) {
+    if (n < 0 || n > (int64_t(1) << 31) || (n > 0 && !recs) || !top_k_ok(k) || !n_out) return HM_E_INVALID;
+    const int64_t m = std::min(k, n);
+    if (m > 0 && !out) return HM_E_INVALID;
+    *n_out = 0;
+    if (m == 0) return HM_OK;
+    std::vector<unsigned long long> kc((size_t)n), cell((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        kc[i] = top_key_count(recs[i].count);
+        cell[i] = recs[i].cell;
+    }
+    std::vector<unsigned> sel;
+    if (int rc = top_select_host(kc.data(), cell.data(), n, m, sel)) return rc;
     for (int64_t j = 0; j < m; j++) out[j] = recs[sel[j]];
     *n_out = m;
     return HM_OK;

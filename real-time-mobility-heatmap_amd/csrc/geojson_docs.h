@@ -26,7 +26,9 @@ namespace hm {
 constexpr int GJ_TEXT_MAX = 40;      // a window text
 constexpr int GJ_PREFIX_LEN = 40;    // {"type":"FeatureCollection","features":[
 #define HM_GJ_PREFIX "{\"type\":\"FeatureCollection\",\"features\":["
-// the longest tile feature: 63 + 11 x 51 + 10 + 18 + 27 + 29 + 39 + 57 + 55 + 2 bytes, and its separator
+// the longest tile feature: 63 + 11 x 51 + 10 + 18 + 27 + 29 + 39 + 57 + 55 + 2 bytes, and its separator; with the near's
+// distance (,"distanceM": and at most 24 bytes of number) GJ_DIST_MAX more
+constexpr int GJ_DIST_MAX = 38;
 constexpr int GJ_TILE_MAX = 872;
 
 // the two window texts of a call, by value (a kernel argument)
@@ -112,9 +114,10 @@ struct JsonW {
 };
 
 // one tile feature from the record's fields and its boundary (vertex k at lat[k * stride], lng[k * stride]); returns
-// its length (without the separator that follows it in the body)
+// its length (without the separator that follows it in the body).  dist_m (optional): the record's distance from a near
+// query's point, appended as the last property ,"distanceM":<repr>; nullptr: the feature as it always was
 HM_HD int tile_feature(uint8_t *dst, const GjTexts &T, uint64_t cell, int64_t count, int64_t n_speed, double sum_speed,
-                       int nv, const double *lat, const double *lng, int64_t stride) {
+                       int nv, const double *lat, const double *lng, int64_t stride, const double *dist_m = nullptr) {
     JsonW w{dst, 0};
     w.lit("{\"type\":\"Feature\",\"geometry\":{\"type\":\"Polygon\",\"coordinates\":[[");
     for (int k = 0; k < nv; k++) {
@@ -145,7 +148,12 @@ HM_HD int tile_feature(uint8_t *dst, const GjTexts &T, uint64_t cell, int64_t co
     w.bytes(T.start, T.start_len);
     w.lit("\",\"windowEnd\":\"");
     w.bytes(T.end, T.end_len);
-    w.lit("\"}}");
+    w.u8('"');
+    if (dist_m) {
+        w.lit(",\"distanceM\":");
+        w.f64(*dist_m);
+    }
+    w.lit("}}");
     return w.n;
 }
 
@@ -160,9 +168,9 @@ HM_HD bool gj_text_ok(const char *s, int len) {
 }
 
 // one position feature; ts_us shifted by off_s seconds of local offset.  -1: a string is not valid UTF-8, or the local
-// year lies outside 1..9999
+// year lies outside 1..9999.  dist_m (optional): as tile_feature's
 HM_HD int position_feature(uint8_t *dst, const uint8_t *ps, int pl, const uint8_t *vs, int vl, int64_t ts_us, int64_t off_s,
-                           double lat, double lon) {
+                           double lat, double lon, const double *dist_m = nullptr) {
     const int64_t s = floordiv(ts_us, 1000000);
     const int us = (int)(ts_us - s * 1000000);
     const int64_t local = s + off_s;
@@ -200,7 +208,12 @@ HM_HD int position_feature(uint8_t *dst, const uint8_t *ps, int pl, const uint8_
         w.dec2(us / 100 % 100);
         w.dec2(us % 100);
     }
-    w.lit("\"}}");
+    w.u8('"');
+    if (dist_m) {
+        w.lit(",\"distanceM\":");
+        w.f64(*dist_m);
+    }
+    w.lit("}}");
     return w.n;
 }
 

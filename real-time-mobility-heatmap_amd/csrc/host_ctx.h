@@ -224,7 +224,8 @@ struct hm_ctx {
     // hm_top_records / hm_window_top / hm_window_geojson_top / hm_positions_density_top (api_top.h, k_top.h): the
     // candidates' key words, the selected keys with their indices and ranks, the records in rank order, a host input's
     // device copy, the window's records in view, the control words -- buffers of its own.  Nothing here is allocated
-    // before the first call.
+    // before the first call.  The near path (api_near.h) borrows kc / cell for its candidates' key words and the
+    // select's scratch (skc, scell, sidx, rank, words, ev); it never touches out, h_out, in, vrecs or info.
     struct Top {
         DevBuf kc, cell, skc, scell, sidx, rank, out, in, vrecs, words;
         void *h_out = nullptr;    // pinned host copy of the ranked records
@@ -235,7 +236,18 @@ struct hm_ctx {
         int64_t info[7] = {0, 0, 0, 0, 0, 0, 0};   // hm_top_info
         int test_grid = 0;        // MOBHEAT_TEST_TOP_GRID: the streaming kernels' largest grid (tests; 0: unset)
     } top;
-    DevBuf keys;                     // k_ingest's event key per row (kernels.h ekey)
+    // hm_positions_near / hm_window_near (api_near.h, k_near.h): the candidates within the radius (records of either
+    // kind; their key words go to the top's kc / cell, the select uses the top's scratch), the ranked records and
+    // distances, the control words -- outputs of its own.  Nothing here is allocated before the first call.
+    struct Near {
+        DevBuf cand, out, dist, words;
+        void *h_out = nullptr, *h_dist = nullptr;   // pinned host copies of the ranked records and distances
+        size_t h_out_cap = 0, h_dist_cap = 0;
+        hipEvent_t ev[2] = {};    // around the emit kernel
+        bool ready = false;
+        int64_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // hm_near_info
+    } near;
+    DevBuf keys;                    // k_ingest's event key per row (kernels.h ekey)
     // k_ingest's fused binning (large direct-path batches): the bins' cursors (RP_BINS + 1 u32: the last stays 0, so
     // that their exclusive scan ends with the total) and the slab capacity; the slabs are parts_sorted
     DevBuf bin_cur;
@@ -392,6 +404,15 @@ static void top_free(hm_ctx *ctx) {
         if (b->p) (void)hipFree(b->p);
     if (T.h_out) (void)hipHostFree(T.h_out);
     for (auto &e : T.ev)
+        if (e) (void)hipEventDestroy(e);
+}
+static void near_free(hm_ctx *ctx) {
+    hm_ctx::Near &N = ctx->near;
+    for (DevBuf *b : {&N.cand, &N.out, &N.dist, &N.words})
+        if (b->p) (void)hipFree(b->p);
+    if (N.h_out) (void)hipHostFree(N.h_out);
+    if (N.h_dist) (void)hipHostFree(N.h_dist);
+    for (auto &e : N.ev)
         if (e) (void)hipEventDestroy(e);
 }
 

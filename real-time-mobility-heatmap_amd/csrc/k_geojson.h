@@ -24,7 +24,7 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
 __global__ __launch_bounds__(256) void k_gj_tile_sizes(GjTexts T, const GrowRec *__restrict__ recs, int64_t n,
                                                        double *__restrict__ vlat, double *__restrict__ vlng,
                                                        int *__restrict__ vn, unsigned *__restrict__ sizes,
-                                                       unsigned long long *words) {
+                                                       unsigned long long *words, const double *__restrict__ dist_m = nullptr) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     unsigned mx = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -36,7 +36,8 @@ __global__ __launch_bounds__(256) void k_gj_tile_sizes(GjTexts T, const GrowRec 
             vlat[(int64_t)k * n + i] = k < nv ? la[k] : 0.0;
             vlng[(int64_t)k * n + i] = k < nv ? lo[k] : 0.0;
         }
-        const unsigned sz = (unsigned)tile_feature(nullptr, T, r.cell, (int64_t)r.count, (int64_t)r.nspeed, r.sspeed, nv, la, lo, 1) + 1u;
+        const unsigned sz = (unsigned)tile_feature(nullptr, T, r.cell, (int64_t)r.count, (int64_t)r.nspeed, r.sspeed, nv, la, lo, 1,
+                                                    dist_m ? dist_m + i : nullptr) + 1u;
         sizes[i + 1] = sz;
         mx = sz > mx ? sz : mx;
     }
@@ -52,7 +53,7 @@ __global__ __launch_bounds__(GJ_THREADS) void k_gj_tile_write(GjTexts T, const G
                                                               const double *__restrict__ vlat, const double *__restrict__ vlng,
                                                               const int *__restrict__ vn,
                                                               const unsigned long long *__restrict__ off,
-                                                              uint8_t *__restrict__ out) {
+                                                              uint8_t *__restrict__ out, const double *__restrict__ dist_m = nullptr) {
     extern __shared__ __attribute__((aligned(16))) uint8_t gj_buf[];   // GJ_THREADS x (the longest feature) + 64
     for (int64_t b0 = (int64_t)blockIdx.x * GJ_THREADS; b0 < n; b0 += (int64_t)gridDim.x * GJ_THREADS) {
         const int64_t b1 = b0 + GJ_THREADS < n ? b0 + GJ_THREADS : n;
@@ -63,7 +64,8 @@ __global__ __launch_bounds__(GJ_THREADS) void k_gj_tile_write(GjTexts T, const G
         if (i < b1) {
             const GrowRec r = recs[i];
             uint8_t *at = gj_buf + (off[i + 1] - base);
-            const int len = tile_feature(at, T, r.cell, (int64_t)r.count, (int64_t)r.nspeed, r.sspeed, vn[i], vlat + i, vlng + i, n);
+            const int len = tile_feature(at, T, r.cell, (int64_t)r.count, (int64_t)r.nspeed, r.sspeed, vn[i], vlat + i, vlng + i, n,
+                                         dist_m ? dist_m + i : nullptr);
             at[len] = i == n - 1 ? ']' : ',';
         }
         if (threadIdx.x == 0) {
@@ -120,19 +122,20 @@ HM_HD bool gj_bucket_offset(const int64_t *ids, const int64_t *offs, int64_t nb,
 }
 
 // one record's feature (dst nullptr: its size), -1: codes outside the dictionaries, bucket absent, bad UTF-8, year range
-__device__ __forceinline__ int gj_position(uint8_t *dst, const PosFeatParams &P, const hm_position_rec &r) {
+__device__ __forceinline__ int gj_position(uint8_t *dst, const PosFeatParams &P, const hm_position_rec &r, const double *dist_m) {
     if ((int64_t)r.provider >= P.n_p || (int64_t)r.vehicle >= P.n_v) return -1;
     int64_t off_s;
     if (!gj_bucket_offset(P.bucket_id, P.bucket_off, P.n_buckets, r.ts_us, off_s)) return -1;
     return position_feature(dst, P.p_arena + P.p_off[r.provider], (int)P.p_len[r.provider], P.v_arena + P.v_off[r.vehicle],
-                            (int)P.v_len[r.vehicle], r.ts_us, off_s, r.lat, r.lon);
+                            (int)P.v_len[r.vehicle], r.ts_us, off_s, r.lat, r.lon, dist_m);
 }
 
 __global__ __launch_bounds__(256) void k_gj_pos_sizes(PosFeatParams P, const hm_position_rec *__restrict__ recs, int64_t n,
-                                                      unsigned *__restrict__ sizes, unsigned long long *words) {
+                                                      unsigned *__restrict__ sizes, unsigned long long *words,
+                                                      const double *__restrict__ dist_m = nullptr) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const int len = gj_position(nullptr, P, recs[i]);
+        const int len = gj_position(nullptr, P, recs[i], dist_m ? dist_m + i : nullptr);
         if (len < 0) atomicAdd(&words[GJW_BAD], 1ull);
         sizes[i + 1] = len < 0 ? 1u : (unsigned)len + 1u;
     }
@@ -141,11 +144,12 @@ __global__ __launch_bounds__(256) void k_gj_pos_sizes(PosFeatParams P, const hm_
 // (one thread per feature straight to HBM, as k_pos_docs: the strings make the lengths vary widely; runs only when
 // k_gj_pos_sizes found no bad record)
 __global__ __launch_bounds__(256) void k_gj_pos_write(PosFeatParams P, const hm_position_rec *__restrict__ recs, int64_t n,
-                                                      const unsigned long long *__restrict__ off, uint8_t *__restrict__ out) {
+                                                      const unsigned long long *__restrict__ off, uint8_t *__restrict__ out,
+                                                      const double *__restrict__ dist_m = nullptr) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         uint8_t *at = out + off[i + 1];
-        const int len = gj_position(at, P, recs[i]);
+        const int len = gj_position(at, P, recs[i], dist_m ? dist_m + i : nullptr);
         if (len < 0) continue;
         at[len] = i == n - 1 ? ']' : ',';
         if (i == n - 1) at[len + 1] = '}';

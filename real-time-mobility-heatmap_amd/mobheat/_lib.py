@@ -104,6 +104,10 @@ class HmView(ctypes.Structure):
     _fields_ = [("west", c_dbl), ("south", c_dbl), ("east", c_dbl), ("north", c_dbl)]
 
 
+class HmNear(ctypes.Structure):
+    _fields_ = [("lat", c_dbl), ("lon", c_dbl), ("max_distance_m", c_dbl)]
+
+
 # hm_state_rec (64 B): one live (cellId, windowStart) key of the tile state
 STATE_REC_DTYPE = np.dtype([("cell", "<u8"), ("window_start_us", "<i8"), ("count", "<i8"), ("n_speed", "<i8"),
                             ("sum_speed", "<f8"), ("sum_lat", "<f8"), ("sum_lon", "<f8"), ("reserved", "<i8")])
@@ -203,6 +207,19 @@ SIGNATURES = {
     "hm_positions_density_top": (c_i32, [c_vp, c_i32, c_i64, _P(HmView), c_i64, c_i32, _P(c_vp), _P(c_i64)]),
     "hm_selftest_top_records": (c_i32, [c_vp, c_i64, c_i64, c_vp, _P(c_i64)]),
     "hm_top_info": (c_i32, [c_vp, c_vp, c_i32]),
+    "hm_near_distances": (c_i32, [_P(HmNear), c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
+    "hm_selftest_near_distances": (c_i32, [_P(HmNear), c_vp, c_vp, c_i64, c_vp]),
+    "hm_positions_near": (c_i32, [c_vp, _P(HmNear), c_i64, c_i64, c_i32, _P(c_vp), _P(c_vp), _P(c_i64)]),
+    "hm_window_near": (c_i32, [c_vp, c_i64, c_i32, _P(HmNear), c_i64, c_i32, _P(c_vp), _P(c_vp), _P(c_i64)]),
+    "hm_selftest_positions_near": (c_i32, [_P(HmNear), c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, _P(c_i64)]),
+    "hm_selftest_tiles_near": (c_i32, [_P(HmNear), c_vp, c_i64, c_i64, c_vp, c_vp, _P(c_i64)]),
+    "hm_near_info": (c_i32, [c_vp, c_vp, c_i32]),
+    "hm_positions_geojson_near": (c_i32, [c_vp, _P(HmPositionDocCfg), _P(HmNear), c_i64, c_i64, c_i32, _P(c_vp), _P(c_vp), _P(c_i64),
+                                          _P(c_vp), _P(c_vp)]),
+    "hm_window_geojson_near": (c_i32, [c_vp, c_i64, c_i32, _P(HmGeojsonCfg), _P(HmNear), c_i64, c_i32, _P(c_vp), _P(c_vp), _P(c_i64),
+                                       _P(c_vp), _P(c_vp)]),
+    "hm_selftest_tile_features_near": (c_i32, [_P(HmGeojsonCfg), c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "hm_selftest_position_features_near": (c_i32, [_P(HmPositionDocCfg), c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "hm_selftest_float_repr_host": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "hm_selftest_float_repr_device": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32]),
     "hm_abi_version": (c_i32, []),
@@ -549,16 +566,24 @@ def geojson_cfg(window_start_text, window_end_text):
     return HmGeojsonCfg(window_start_text=a, start_len=len(a), window_end_text=b, end_len=len(b)), (a, b)
 
 
-def tile_features_selftest(recs, window_start_text, window_end_text):
-    """Host execution of the GPU tile-feature encoder on STATE_REC_DTYPE records (no GPU): (body uint8, offsets int64)."""
+def tile_features_selftest(recs, window_start_text, window_end_text, dist_m=None):
+    """Host execution of the GPU tile-feature encoder on STATE_REC_DTYPE records (no GPU): (body uint8, offsets int64).
+    dist_m (float64 per record): hm_selftest_tile_features_near, the features with distanceM as their last property."""
     lib = load()
     recs = np.ascontiguousarray(recs, dtype=STATE_REC_DTYPE)
     cfg, keep = geojson_cfg(window_start_text, window_end_text)
-    cap = 64 + 880 * recs.size
+    cap = 64 + 920 * recs.size
     buf = np.zeros(cap, np.uint8)
     offs = np.zeros(recs.size + 1, np.int64)
-    check(lib.hm_selftest_tile_features(ctypes.byref(cfg), ptr(recs) if recs.size else None, recs.size, ptr(buf), cap,
-                                        ptr(offs)), None, "hm_selftest_tile_features")
+    if dist_m is None:
+        check(lib.hm_selftest_tile_features(ctypes.byref(cfg), ptr(recs) if recs.size else None, recs.size, ptr(buf), cap,
+                                            ptr(offs)), None, "hm_selftest_tile_features")
+    else:
+        d = np.ascontiguousarray(dist_m, dtype=np.float64)
+        assert d.size == recs.size
+        check(lib.hm_selftest_tile_features_near(ctypes.byref(cfg), ptr(recs) if recs.size else None, recs.size,
+                                                 ptr(d) if d.size else None, ptr(buf), cap, ptr(offs)), None,
+              "hm_selftest_tile_features_near")
     return buf[:geojson_body_len(offs)].copy(), offs
 
 
@@ -582,7 +607,7 @@ def bucket_cfg(bucket_ids, tz=None):
     return cfg, (bi, bo)
 
 
-def position_features_selftest(recs, providers, vehicles, bucket_ids, bucket_offset_s):
+def position_features_selftest(recs, providers, vehicles, bucket_ids, bucket_offset_s, dist_m=None):
     """Host execution of the GPU position-feature encoder (no GPU) on POSITION_REC_DTYPE records, the two dictionaries
     ((n, offsets, bytes), so that any byte string can be given) and the bucket table: (body uint8, offsets int64)."""
     lib = load()
@@ -591,11 +616,18 @@ def position_features_selftest(recs, providers, vehicles, bucket_ids, bucket_off
     bi = np.ascontiguousarray(bucket_ids, np.int64)
     bo = np.ascontiguousarray(bucket_offset_s, np.int64)
     cfg.n_buckets, cfg.bucket_ids, cfg.bucket_offset_s = bi.size, ptr(bi) if bi.size else None, ptr(bo) if bo.size else None
-    cap = 64 + recs.size * 256 + 12 * recs.size * int(max(keep[1].size, 1) + max(keep[3].size, 1))
+    cap = 64 + recs.size * 300 + 12 * recs.size * int(max(keep[1].size, 1) + max(keep[3].size, 1))
     buf = np.zeros(cap, np.uint8)
     offs = np.zeros(recs.size + 1, np.int64)
-    check(lib.hm_selftest_position_features(ctypes.byref(cfg), ptr(recs) if recs.size else None, recs.size, ptr(buf), cap,
-                                            ptr(offs)), None, "hm_selftest_position_features")
+    if dist_m is None:
+        check(lib.hm_selftest_position_features(ctypes.byref(cfg), ptr(recs) if recs.size else None, recs.size, ptr(buf), cap,
+                                                ptr(offs)), None, "hm_selftest_position_features")
+    else:   # (the features with distanceM as their last property)
+        d = np.ascontiguousarray(dist_m, dtype=np.float64)
+        assert d.size == recs.size
+        check(lib.hm_selftest_position_features_near(ctypes.byref(cfg), ptr(recs) if recs.size else None, recs.size,
+                                                     ptr(d) if d.size else None, ptr(buf), cap, ptr(offs)), None,
+              "hm_selftest_position_features_near")
     return buf[:geojson_body_len(offs)].copy(), offs
 
 
@@ -698,4 +730,70 @@ def state_recs_at(p, n, copy=True):
     if n == 0:
         return np.zeros(0, STATE_REC_DTYPE)
     recs = np.ctypeslib.as_array(ctypes.cast(p, _P(ctypes.c_uint8)), shape=(n * STATE_REC_DTYPE.itemsize,)).view(STATE_REC_DTYPE)
+    return recs.copy() if copy else recs
+
+
+# ---- radius queries (csrc/k_near.h) ----
+HM_EARTH_RADIUS_M = 6378100.0
+
+
+def near_struct(lat, lon, max_distance_m=float("inf")):
+    """hm_near of a query point in degrees and a radius in metres; validity is the library's to judge (HM_E_INVALID)."""
+    return HmNear(lat=float(lat), lon=float(lon), max_distance_m=float(max_distance_m))
+
+
+def near_distances_selftest(lat0, lon0, lat, lon, device=None):
+    """The distance in metres from (lat0, lon0) to every (lat[i], lon[i]): host execution of the kernels' code (no GPU), or
+    on GPU `device` (hm_near_distances)."""
+    lib = load()
+    lat = np.ascontiguousarray(lat, dtype=np.float64).reshape(-1)
+    lon = np.ascontiguousarray(lon, dtype=np.float64).reshape(-1)
+    assert lat.size == lon.size
+    q = near_struct(lat0, lon0)
+    out = np.zeros(lat.size, np.float64)
+    p = (lambda a: ptr(a) if a.size else None)
+    if device is None:
+        check(lib.hm_selftest_near_distances(ctypes.byref(q), p(lat), p(lon), lat.size, p(out)), None, "hm_selftest_near_distances")
+    else:
+        check(lib.hm_near_distances(ctypes.byref(q), p(lat), p(lon), lat.size, HM_MEM_HOST, int(device), p(out)), None,
+              "hm_near_distances")
+    return out
+
+
+def _near_selftest(fn, name, dtype, q, recs, k, *lead):
+    lib = load()
+    recs = np.ascontiguousarray(recs, dtype=dtype)
+    room = max(min(int(k), recs.size), 1)
+    out, dist, n = np.zeros(room, dtype), np.zeros(room, np.float64), c_i64()
+    check(getattr(lib, fn)(ctypes.byref(q), *lead, ptr(recs) if recs.size else None, recs.size, int(k), ptr(out), ptr(dist),
+                           ctypes.byref(n)), None, name)
+    return out[:n.value].copy(), dist[:n.value].copy()
+
+
+def positions_near_selftest(recs, lat, lon, max_distance_m=float("inf"), k=HM_TOP_MAX, since_us=None):
+    """Host execution of the near query (no GPU) on POSITION_REC_DTYPE records: (the first min(k, kept) records nearest
+    first, then provider << 32 | vehicle ascending, then input index; their distances in metres)."""
+    return _near_selftest("hm_selftest_positions_near", "hm_selftest_positions_near", POSITION_REC_DTYPE,
+                          near_struct(lat, lon, max_distance_m), recs, k, INT64_MIN if since_us is None else int(since_us))
+
+
+def tiles_near_selftest(recs, lat, lon, max_distance_m=float("inf"), k=HM_TOP_MAX):
+    """The same on STATE_REC_DTYPE records by their centroid (sum_lat / count, sum_lon / count); ties by cell ascending."""
+    return _near_selftest("hm_selftest_tiles_near", "hm_selftest_tiles_near", STATE_REC_DTYPE, near_struct(lat, lon, max_distance_m),
+                          recs, k)
+
+
+def doubles_at(p, n, copy=True):
+    """n doubles at host pointer p (a copy, or a view of the library's buffer)."""
+    if n == 0:
+        return np.zeros(0, np.float64)
+    a = np.ctypeslib.as_array(ctypes.cast(p, _P(ctypes.c_double)), shape=(n,))
+    return a.copy() if copy else a
+
+
+def position_recs_at(p, n, copy=True):
+    """n hm_position_rec at host pointer p as a POSITION_REC_DTYPE array (a copy, or a view of the library's buffer)."""
+    if n == 0:
+        return np.zeros(0, POSITION_REC_DTYPE)
+    recs = np.ctypeslib.as_array(ctypes.cast(p, _P(ctypes.c_uint8)), shape=(n * POSITION_REC_DTYPE.itemsize,)).view(POSITION_REC_DTYPE)
     return recs.copy() if copy else recs

@@ -744,6 +744,86 @@ class HeatmapEngine:
         return {"candidates": v[0], "returned": v[1], "count_passes": v[2], "cell_passes": v[3], "index_passes": v[4],
                 "tied": v[5], "device_us": v[6]}
 
+    # ---- radius queries: the vehicles / tiles nearest a point (hm_*_near; csrc/k_near.h) ----
+    def positions_near(self, lat, lon, max_distance_m=float("inf"), k=_lib.HM_TOP_MAX, since_us=None, copy=True):
+        """The k vehicles of the positions state nearest (lat, lon) within max_distance_m metres (closed; inf: no limit),
+        among those with ts_us >= since_us (None: all): (records POSITION_REC_DTYPE, dist_m float64), nearest first, ties
+        by provider code << 32 | vehicle code ascending -- distance (readside.near_distance_m, bit for bit), filter,
+        selection and order on the GPU in one call (hm_positions_near).  copy=False: views of the library's pinned
+        buffers, valid until the next call on this engine."""
+        q = _lib.near_struct(lat, lon, max_distance_m)
+        since = _lib.INT64_MIN if since_us is None else int(since_us)
+        p, d, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        check(self._lib.hm_positions_near(self._ctx, ctypes.byref(q), since, int(k), HM_MEM_HOST, ctypes.byref(p), ctypes.byref(d),
+                                          ctypes.byref(n)), self._ctx, "hm_positions_near")
+        return _lib.position_recs_at(p, n.value, copy), _lib.doubles_at(d, n.value, copy)
+
+    def window_near(self, lat, lon, max_distance_m=float("inf"), k=_lib.HM_TOP_MAX, window_start_us=None, res=None, copy=True):
+        """The k tiles of one live window (None: the newest) at resolution res <= h3_res (None: h3_res) whose centroid
+        (sum_lat / count, sum_lon / count, as window_tiles) is nearest (lat, lon) within max_distance_m: (records
+        STATE_REC_DTYPE, dist_m float64), nearest first, ties by cell ascending (hm_window_near).  A window that is not
+        live gives no record."""
+        res = self.h3_res if res is None else int(res)
+        if window_start_us is None:
+            ws, _ = self.live_windows()
+            window_start_us = ws[-1] if ws.size else 0
+        q = _lib.near_struct(lat, lon, max_distance_m)
+        p, d, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        check(self._lib.hm_window_near(self._ctx, int(window_start_us), res, ctypes.byref(q), int(k), HM_MEM_HOST, ctypes.byref(p),
+                                       ctypes.byref(d), ctypes.byref(n)), self._ctx, "hm_window_near")
+        return _lib.state_recs_at(p, n.value, copy), _lib.doubles_at(d, n.value, copy)
+
+    def _near_body(self, pb, po, pr, pd, n, dtype, copy, with_records):
+        body = self._geojson_body(pb, po, n, copy)
+        if not with_records:
+            return body
+        recs = (_lib.position_recs_at if dtype is _lib.POSITION_REC_DTYPE else _lib.state_recs_at)(pr, n)
+        offs = np.ctypeslib.as_array(ctypes.cast(po, ctypes.POINTER(ctypes.c_int64)), shape=(n + 1,)).copy()
+        return body, recs, _lib.doubles_at(pd, n), offs
+
+    def positions_near_geojson(self, lat, lon, max_distance_m=float("inf"), k=_lib.HM_TOP_MAX, since_us=None, tz=None, copy=True,
+                               with_records=False):
+        """The body of a /api/positions/near route: json.dumps(readside.positions_near_from_engine(...), separators=(",",
+        ":")) as bytes -- positions_near's records never leave the device between the select and the feature encoder
+        (hm_positions_geojson_near); every feature carries "distanceM" as its last property.  tz / copy as
+        positions_geojson; with_records: (body, records in feature order, dist_m, offsets) instead."""
+        cfg, keep = _lib.bucket_cfg(self.positions_buckets(), tz)
+        q = _lib.near_struct(lat, lon, max_distance_m)
+        since = _lib.INT64_MIN if since_us is None else int(since_us)
+        pb, po, pr, pd, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        check(self._lib.hm_positions_geojson_near(self._ctx, ctypes.byref(cfg), ctypes.byref(q), since, int(k), HM_MEM_HOST,
+                                                  ctypes.byref(pb), ctypes.byref(po), ctypes.byref(n),
+                                                  ctypes.byref(pr) if with_records else None,
+                                                  ctypes.byref(pd) if with_records else None),
+              self._ctx, "hm_positions_geojson_near")
+        return self._near_body(pb, po, pr, pd, n.value, _lib.POSITION_REC_DTYPE, copy, with_records)
+
+    def window_near_geojson(self, lat, lon, max_distance_m=float("inf"), k=_lib.HM_TOP_MAX, window_start_us=None, res=None, tz=None,
+                            copy=True, with_records=False):
+        """The body of a /api/tiles/near route: json.dumps(readside.tiles_near_from_engine(...), separators=(",", ":")) as
+        bytes, rolled up, ranked by the centroid's distance and encoded on the GPU in one call (hm_window_geojson_near);
+        every feature carries "distanceM" as its last property.  The window texts as window_geojson's."""
+        res = self.h3_res if res is None else int(res)
+        if window_start_us is None:
+            ws, _ = self.live_windows()
+            window_start_us = ws[-1] if ws.size else 0
+        window_start_us = int(window_start_us)
+        cfg, keep = _lib.geojson_cfg(_lib.wall_iso(window_start_us, tz), _lib.wall_iso(window_start_us + self.tile_us, tz))
+        q = _lib.near_struct(lat, lon, max_distance_m)
+        pb, po, pr, pd, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        check(self._lib.hm_window_geojson_near(self._ctx, window_start_us, res, ctypes.byref(cfg), ctypes.byref(q), int(k),
+                                               HM_MEM_HOST, ctypes.byref(pb), ctypes.byref(po), ctypes.byref(n),
+                                               ctypes.byref(pr) if with_records else None,
+                                               ctypes.byref(pd) if with_records else None),
+              self._ctx, "hm_window_geojson_near")
+        return self._near_body(pb, po, pr, pd, n.value, STATE_REC_DTYPE, copy, with_records)
+
+    def near_info(self):
+        v = (ctypes.c_int64 * 8)()
+        check(self._lib.hm_near_info(self._ctx, v, 8), self._ctx, "hm_near_info")
+        return {"scanned": v[0], "kept_since": v[1], "nan": v[2], "within": v[3], "returned": v[4], "passes": v[5],
+                "emit_us": v[6], "select_us": v[7]}
+
     def encode_tile_updates_device(self, city, ttl_minutes):
         """The same, left on the device: (device pointer of the bytes, of the offsets, n statements)."""
         n = ctypes.c_int64()

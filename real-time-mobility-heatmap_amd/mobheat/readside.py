@@ -391,3 +391,144 @@ def tiles_top_from_engine(engine, k, res=None, city="boston", tz=None, view=None
     at resolution res (in view, when a view is given -- the view comes first), in rank order; tiles_latest_from_engine's
     features, filtered, ranked and cut here in Python.  The comparison form of tiles_latest_body(top=k)."""
     return _top_features(tiles_latest_from_engine(engine, res, city, tz, view), k)
+
+
+# ---- radius queries: what is around a point, nearest first (HeatmapEngine.positions_near / window_near, csrc/k_near.h) ----
+EARTH_RADIUS_M = _lib.HM_EARTH_RADIUS_M   # MongoDB's sphere
+_DEG = 0.017453292519943295               # the double math.radians multiplies by
+
+
+def near_distance_m(lat0, lon0, lat, lon):
+    """The distance in metres from (lat0, lon0) to (lat, lon), degrees: the comparison form of the device's distance
+    (include/mobheat.h), the same binary64 operations in the same order, one rounding each -- sin / cos / asin through the
+    running glibc (oracle.h3_oracle.libm), sqrt the correctly rounded one.  lat / lon: scalars (a float comes back) or
+    arrays (each element on its own, the same operations: the vectorised form of one candidate at a time).  Needs the
+    repository's oracle/ package on sys.path (the checker's libm binding); the engine's own calls do not."""
+    from oracle.h3_oracle import libm
+    scalar = np.ndim(lat) == 0 and np.ndim(lon) == 0
+    lat = np.atleast_1d(np.asarray(lat, dtype=np.float64))
+    lon = np.atleast_1d(np.asarray(lon, dtype=np.float64))
+    lat, lon = np.broadcast_arrays(lat, lon)
+    p0 = np.float64(lat0) * np.float64(_DEG)
+    with np.errstate(invalid="ignore", over="ignore"):
+        p1 = lat * np.float64(_DEG)
+        s_h, _ = libm("sincos", (p1 - p0) * 0.5)
+        s_l, _ = libm("sincos", ((lon - np.float64(lon0)) * np.float64(_DEG)) * 0.5)
+        _, c0 = libm("sincos", np.full(1, p0))
+        _, c1 = libm("sincos", p1)
+        a = s_h * s_h + (c0[0] * c1) * (s_l * s_l)
+        r = np.sqrt(a)
+        r = np.where(r > 1.0, 1.0, r)
+        d = (2.0 * EARTH_RADIUS_M) * libm("asin", r)
+    return float(d[0]) if scalar else d
+
+
+def near_valid(lat, lon, max_distance_m):
+    """lat in [-90, 90], lon in [-180, 180], max_distance_m >= 0 or +inf, none NaN."""
+    return -90.0 <= float(lat) <= 90.0 and -180.0 <= float(lon) <= 180.0 and float(max_distance_m) >= 0.0
+
+
+def near_from_query(lat, lon, r=None):
+    """The query of a route's lat=, lon= and r= (metres; None or "": no limit) strings: (lat, lon, max_distance_m) as
+    floats.  ValueError for anything that is not a number or not a valid query."""
+    try:
+        q = (float(lat), float(lon), float("inf") if r is None or str(r) == "" else float(r))
+    except (TypeError, ValueError):
+        raise ValueError(f"near query ({lat!r}, {lon!r}, {r!r}): not a number") from None
+    if not near_valid(*q):
+        raise ValueError(f"near query {q!r}: -90 <= lat <= 90, -180 <= lon <= 180 and r >= 0 expected")
+    return q
+
+
+def near_order(dist, key, k):
+    """The input indices of the first min(k, n) candidates in the near's order: distance ascending (non-negative doubles by
+    their bits), then key ascending as uint64, then input index."""
+    dist, key = np.asarray(dist, dtype=np.float64), np.asarray(key).astype(np.uint64)
+    k = int(k)
+    if not 0 <= k <= TOP_MAX:
+        raise ValueError(f"k = {k} outside 0..{TOP_MAX}")
+    return np.lexsort((np.arange(dist.size), key, dist.view(np.uint64)))[:k]
+
+
+def near_of(lat0, lon0, lat, lon, key, max_distance_m=float("inf"), k=TOP_MAX, keep=None):
+    """(input indices, distances) of the near query over candidate coordinates in numpy with near_distance_m: the
+    candidates with keep (None: all), a distance that is not NaN and <= max_distance_m, the first k of near_order."""
+    d = near_distance_m(lat0, lon0, np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64))
+    ok = (d == d) & (d <= float(max_distance_m))
+    if keep is not None:
+        ok &= np.asarray(keep, dtype=bool)
+    idx = np.flatnonzero(ok)
+    o = near_order(d[idx], np.asarray(key).astype(np.uint64)[idx], k)
+    return idx[o], d[idx][o]
+
+
+def positions_near_of(records, lat, lon, max_distance_m=float("inf"), k=TOP_MAX, since_us=None):
+    """near(records, ...) in numpy on POSITION_REC_DTYPE records: (records, dist_m) -- the comparison form of
+    HeatmapEngine.positions_near."""
+    r = np.asarray(records, dtype=_lib.POSITION_REC_DTYPE)
+    key = (r["provider"].astype(np.uint64) << np.uint64(32)) | r["vehicle"].astype(np.uint64)
+    keep = None if since_us is None else r["ts_us"] >= int(since_us)
+    idx, d = near_of(lat, lon, r["lat"], r["lon"], key, max_distance_m, k, keep)
+    return r[idx], d
+
+
+def tiles_near_of(records, lat, lon, max_distance_m=float("inf"), k=TOP_MAX):
+    """The same on STATE_REC_DTYPE records by their centroid (sum_lat / count, sum_lon / count): the comparison form of
+    HeatmapEngine.window_near."""
+    r = np.asarray(records, dtype=_lib.STATE_REC_DTYPE)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        cnt = r["count"].astype(np.uint64).astype(np.float64)
+        idx, d = near_of(lat, lon, r["sum_lat"] / cnt, r["sum_lon"] / cnt, r["cell"], max_distance_m, k)
+    return r[idx], d
+
+
+def _near_features(features, lat0, lon0, point, key, max_distance_m, k, keep=None):
+    """the features within the radius, nearest first, each with properties.distanceM as its last property"""
+    if not near_valid(lat0, lon0, max_distance_m):
+        raise ValueError(f"invalid near query {(lat0, lon0, max_distance_m)!r}")
+    pts = [point(f) for f in features]
+    idx, d = near_of(lat0, lon0, [p[0] for p in pts], [p[1] for p in pts], [key(f) for f in features], max_distance_m, k, keep)
+    out = []
+    for i, di in zip(idx, d):
+        f = dict(features[int(i)])
+        f["properties"] = dict(f["properties"], distanceM=float(di))
+        out.append(f)
+    return {"type": "FeatureCollection", "features": out}
+
+
+def positions_near_from_engine(engine, lat, lon, max_distance_m=float("inf"), k=TOP_MAX, since_us=None, tz=None):
+    """The FeatureCollection a /api/positions/near?lat=&lon=&r=&n= route returns: positions_latest_from_engine's features,
+    filtered by since_us and the radius, ranked (distance, then provider code << 32 | vehicle code) and cut here in Python,
+    with distanceM added.  The comparison form of positions_near_body."""
+    recs, providers, vehicles = engine.positions()
+    code = {(providers[int(r["provider"])], vehicles[int(r["vehicle"])]): (int(r["provider"]) << 32) | int(r["vehicle"]) for r in recs}
+    ts = {(providers[int(r["provider"])], vehicles[int(r["vehicle"])]): int(r["ts_us"]) for r in recs}
+    f = positions_latest_from_engine(engine, tz)["features"]
+    name = [(x["properties"]["provider"], x["properties"]["vehicleId"]) for x in f]
+    keep = None if since_us is None else [ts[m] >= int(since_us) for m in name]
+    by_name = dict(zip(map(id, f), name))
+    return _near_features(f, lat, lon, lambda x: (x["geometry"]["coordinates"][1], x["geometry"]["coordinates"][0]),
+                          lambda x: code[by_name[id(x)]], max_distance_m, k, keep)
+
+
+def tiles_near_from_engine(engine, lat, lon, max_distance_m=float("inf"), k=TOP_MAX, res=None, city="boston", tz=None):
+    """The FeatureCollection a /api/tiles/near route returns: tiles_latest_from_engine's features of the newest live window
+    at resolution res, ranked by the distance of the tile document's centroid (then cell) and cut here in Python, with
+    distanceM added.  The comparison form of tiles_near_body."""
+    docs = tile_docs_from_engine(engine, res, city, tz)
+    centroid = {d["cellId"]: (d["centroid"]["coordinates"][1], d["centroid"]["coordinates"][0]) for d in docs}
+    f = tiles_latest_collection(docs, engine.device)["features"]
+    return _near_features(f, lat, lon, lambda x: centroid[x["properties"]["cellId"]], lambda x: _cell_int(x["properties"]["cellId"]),
+                          max_distance_m, k)
+
+
+def positions_near_body(engine, lat, lon, max_distance_m=float("inf"), k=TOP_MAX, since_us=None, tz=None):
+    """The response body of a /api/positions/near route as bytes: json.dumps(positions_near_from_engine(...), separators=
+    (",", ":")), selected, ranked and encoded on the GPU (HeatmapEngine.positions_near_geojson)."""
+    return engine.positions_near_geojson(lat, lon, max_distance_m, k, since_us, tz)
+
+
+def tiles_near_body(engine, lat, lon, max_distance_m=float("inf"), k=TOP_MAX, res=None, tz=None):
+    """The response body of a /api/tiles/near route as bytes: json.dumps(tiles_near_from_engine(...), separators=(",", ":")),
+    rolled up, ranked and encoded on the GPU (HeatmapEngine.window_near_geojson)."""
+    return engine.window_near_geojson(lat, lon, max_distance_m, k, None, res, tz)
