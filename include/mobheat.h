@@ -35,6 +35,7 @@
  *   hm_window_geojson_view / hm_positions_geojson_view / hm_cells_in_view -- the same for a client's map viewport.
  *   hm_window_raster             -- a live window's counts per pixel of a grid, for z/x/y raster tiles of the heatmap.
  *   hm_positions_density*        -- the positions state grouped into H3 cells: vehicles per cell at any resolution.
+ *   hm_*_near / hm_*_within      -- what is around a point (radius queries) and what is inside polygon zones (geofences).
  */
 #ifndef MOBHEAT_H
 #define MOBHEAT_H
@@ -808,6 +809,80 @@ int hm_selftest_tiles_near(const hm_near *q, const hm_state_rec *recs, int64_t n
  * microseconds of the emit kernel, [7] of the select and the scatter (HIP events, as the top's).  All 0 before the first
  * call. */
 int hm_near_info(const hm_ctx *ctx, int64_t *v, int32_t n);
+
+/* ---- polygon geofences: the vehicles / tiles inside zones (the other half of what the reference's 2dsphere indexes
+ * serve: $geoWithin: {$geometry: Polygon}) ----
+ * A zone set is n_zones zones; zone z is the rings zone_rings[z] .. zone_rings[z + 1] - 1 (a GeoJSON Polygon's exterior
+ * and holes; a MultiPolygon is one zone of all its rings); ring r is the vertices ring_verts[r] .. ring_verts[r + 1] - 1
+ * of (lat, lon) in degrees, at least 3, WITHOUT the repeated closing vertex; edge k of a ring runs from its vertex k to
+ * its vertex (k + 1) mod n.  Edges are straight in the (lon, lat) plane, as RFC 7946 and the reference page's map draw
+ * them (MongoDB's geodesic edges are not reproduced); a zone across the antimeridian is the caller's to split, longitudes
+ * are never normalised; ring orientation is free.
+ *   membership  a point (lat, lon) is in a zone iff it crosses an odd number of the zone's edges, all rings together
+ *               (holes need no case).  Edge (a, b), in binary64, one rounding per operation in this order, no FMA:
+ *                 a.lat == b.lat: never crossed;  else the endpoints ordered so that a.lat < b.lat
+ *                 straddles = (a.lat <= lat) && (lat < b.lat)
+ *                 crossed   = straddles && ((b.lon - a.lon) * (lat - a.lat) > (lon - a.lon) * (b.lat - a.lat))
+ *               The ordering makes two zones that share an edge evaluate one predicate for it: zones that tile a region
+ *               hold each of its points an odd number of times.  A NaN coordinate is in no zone.
+ *               mobheat/readside.py points_in_zones is the same lines in numpy; there is no tolerance anywhere.
+ *   overlap     per-zone totals count a point in EVERY zone that contains it; a kept record's label is the LOWEST-index
+ *               zone that contains it.
+ *   a tile's point is its centroid as the near queries take it (sum_lat / count, sum_lon / count, one division each).
+ * Validation: n_zones <= HM_ZONES_MAX, at most HM_ZONE_VERTS_MAX vertices in total, zone_rings[0] = ring_verts[0] = 0,
+ * every zone at least one ring, every ring at least 3 vertices, every vertex finite with -90 <= lat <= 90 and
+ * -180 <= lon <= 180; anything else: HM_E_INVALID, nothing touched, the message names the limit.  The zone arrays are
+ * host memory and are read during the call only. */
+#define HM_ZONES_MAX 4096
+#define HM_ZONE_VERTS_MAX 65536
+typedef struct { int32_t n_zones; const int32_t *zone_rings;  /* n_zones + 1: a zone's rings */
+                 const int32_t *ring_verts;                    /* n_rings + 1: a ring's vertices */
+                 const double *lat, *lon; } hm_zones;          /* host memory */
+typedef struct { int64_t n;          /* vehicles / tiles in the zone */
+                 int64_t count;      /* vehicles again / the tiles' summed count */
+                 int64_t n_speed; double sum_speed;            /* tiles: summed; positions: 0, +0.0 */
+                 int64_t newest_us;  /* positions: the zone's newest ts_us (INT64_MIN when empty); tiles: 0 */
+                 int64_t reserved; } hm_zone_rec;              /* 48 B */
+/* first_zone_i32[i] = the lowest zone that contains (lat[i], lon[i]) or -1, hits_u32[i] = how many zones contain it, on
+ * GPU `device`; memory / device as hm_near_distances (with HM_MEM_DEVICE lat, lon and the two outputs are device
+ * pointers; the zone set is host memory always). */
+int hm_points_in_zones(const hm_zones *zones, const double *lat, const double *lon, int64_t n, int32_t memory, int32_t device,
+                       int32_t *first_zone_i32, uint32_t *hits_u32);
+/* Host execution of the same predicate (no GPU, no reject ahead of the edges). */
+int hm_selftest_points_in_zones(const hm_zones *zones, const double *lat, const double *lon, int64_t n, int32_t *first_zone_i32,
+                                uint32_t *hits_u32);
+/* The vehicles of the positions state S with ts_us >= since_us (hm_positions_density's meaning; INT64_MIN keeps all)
+ * that are in at least one zone, in one scan of the pair table: *n of them; with recs != NULL the records and their
+ * labels (a set: in no particular order; library-owned, device or pinned host memory per out_memory, valid until the
+ * next call on the context); recs == NULL: totals only (zone may be NULL then).  totals (host memory, n_zones records,
+ * may be NULL): every zone's n = count = its vehicles, newest_us their newest ts_us.  State errors as
+ * hm_positions_near's (a shard context: HM_E_UNSUPPORTED; between stage calls: HM_E_STATE); an empty S: *n = 0. */
+int hm_positions_within(hm_ctx *ctx, const hm_zones *zones, int64_t since_us, int32_t out_memory, hm_zone_rec *totals,
+                        const hm_position_rec **recs, const int32_t **zone, int64_t *n);
+/* The same over the tiles of hm_window_rollup(window_start_us, res) by their centroid: totals n = the zone's tiles,
+ * count / n_speed / sum_speed their sums (sum_speed an fp64 sum in no particular order).  hm_window_near's rules: a
+ * window that is not live: *n = 0 and zero totals; a shard context: HM_E_UNSUPPORTED; between stage calls: HM_E_STATE;
+ * res outside 0..h3_res: HM_E_INVALID. */
+int hm_window_within(hm_ctx *ctx, int64_t window_start_us, int32_t res, const hm_zones *zones, int32_t out_memory,
+                     hm_zone_rec *totals, const hm_state_rec **recs, const int32_t **zone, int64_t *n);
+/* hm_positions_geojson_view / hm_window_geojson_view with a zone set in place of the view: the features of the records
+ * in at least one zone (every vehicle of S / every tile of the window), the feature bytes unchanged (no new property),
+ * the records never leaving the device between the scan and the encoder; none kept: the 42-byte empty body. */
+int hm_positions_geojson_within(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t out_memory, const uint8_t **bytes,
+                                const int64_t **offsets, int64_t *n, const hm_position_rec **recs, const hm_zones *zones);
+int hm_window_geojson_within(hm_ctx *ctx, int64_t window_start_us, int32_t res, const hm_geojson_cfg *cfg, int32_t out_memory,
+                             const uint8_t **bytes, const int64_t **offsets, int64_t *n, const hm_state_rec **recs,
+                             const hm_zones *zones);
+/* Host execution of the two queries on caller records (no GPU): the kept records in input order with their labels
+ * (out / zone: room for n, or both NULL), the totals (n_zones records, may be NULL), *n_out = the records kept. */
+int hm_selftest_positions_within(const hm_zones *zones, int64_t since_us, const hm_position_rec *recs, int64_t n,
+                                 hm_zone_rec *totals, hm_position_rec *out, int32_t *zone, int64_t *n_out);
+int hm_selftest_tiles_within(const hm_zones *zones, const hm_state_rec *recs, int64_t n, hm_zone_rec *totals, hm_state_rec *out,
+                             int32_t *zone, int64_t *n_out);
+/* up to n of, for the last within call on the context: [0] pair-table slots / roll-up records scanned, [1] kept by
+ * since_us, [2] in at least one zone, [3] the set's zones, [4] its vertices, [5] device microseconds of the scan (HIP
+ * events around it).  All 0 before the first call. */
+int hm_within_info(const hm_ctx *ctx, int64_t *v, int32_t n);
 
 /* json.dumps(x) of n doubles -- CPython's float.__repr__, NaN / Infinity / -Infinity for the non-finite -- as the GeoJSON
  * encoders write them (csrc/float_repr.h), executed on the host and on GPU `device` (test entry points): value i's

@@ -8,7 +8,7 @@ struct UdfState {
     bool ready = false;
     int64_t last_exact = 0;   // hm_latlng_to_cell: inputs the fast path handed to the exact path (last call)
     hipStream_t stream = nullptr;
-    DevBuf in0, in1, out0, out1, out2, slow;
+    DevBuf in0, in1, out0, out1, out2, slow, zones;
 };
 static std::mutex g_udf_mu;
 static UdfState g_udf[64];

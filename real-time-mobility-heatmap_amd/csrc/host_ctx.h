@@ -247,6 +247,18 @@ struct hm_ctx {
         bool ready = false;
         int64_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // hm_near_info
     } near;
+    // hm_positions_within / hm_window_within (api_within.h, k_within.h): the packed zone set, the kept records (of either
+    // kind) and their labels, the zones' totals, the control words -- buffers of its own.  Nothing here is allocated
+    // before the first call.
+    struct Within {
+        DevBuf zones, out, zone, tot, words;
+        void *h_zones = nullptr, *h_out = nullptr, *h_zone = nullptr, *h_tot = nullptr;   // pinned: the set packed, the outputs' copies
+        size_t h_zones_cap = 0, h_out_cap = 0, h_zone_cap = 0, h_tot_cap = 0;
+        hipEvent_t ev[2] = {};    // around the scan
+        bool ready = false;
+        int tot_zones = 0;        // the zones whose totals the last scan left in h_tot (0: it did not run)
+        int64_t info[6] = {0, 0, 0, 0, 0, 0};   // hm_within_info
+    } within;
     DevBuf keys;                    // k_ingest's event key per row (kernels.h ekey)
     // k_ingest's fused binning (large direct-path batches): the bins' cursors (RP_BINS + 1 u32: the last stays 0, so
     // that their exclusive scan ends with the total) and the slab capacity; the slabs are parts_sorted
@@ -413,6 +425,15 @@ static void near_free(hm_ctx *ctx) {
     if (N.h_out) (void)hipHostFree(N.h_out);
     if (N.h_dist) (void)hipHostFree(N.h_dist);
     for (auto &e : N.ev)
+        if (e) (void)hipEventDestroy(e);
+}
+static void within_free(hm_ctx *ctx) {
+    hm_ctx::Within &W = ctx->within;
+    for (DevBuf *b : {&W.zones, &W.out, &W.zone, &W.tot, &W.words})
+        if (b->p) (void)hipFree(b->p);
+    for (void *h : {W.h_zones, W.h_out, W.h_zone, W.h_tot})
+        if (h) (void)hipHostFree(h);
+    for (auto &e : W.ev)
         if (e) (void)hipEventDestroy(e);
 }
 

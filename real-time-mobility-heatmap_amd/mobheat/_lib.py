@@ -108,6 +108,15 @@ class HmNear(ctypes.Structure):
     _fields_ = [("lat", c_dbl), ("lon", c_dbl), ("max_distance_m", c_dbl)]
 
 
+class HmZones(ctypes.Structure):
+    _fields_ = [("n_zones", c_i32), ("zone_rings", c_vp), ("ring_verts", c_vp), ("lat", c_vp), ("lon", c_vp)]
+
+
+# hm_zone_rec (48 B): one zone's totals of a within query
+ZONE_REC_DTYPE = np.dtype([("n", "<i8"), ("count", "<i8"), ("n_speed", "<i8"), ("sum_speed", "<f8"), ("newest_us", "<i8"),
+                           ("reserved", "<i8")])
+assert ZONE_REC_DTYPE.itemsize == 48
+
 # hm_state_rec (64 B): one live (cellId, windowStart) key of the tile state
 STATE_REC_DTYPE = np.dtype([("cell", "<u8"), ("window_start_us", "<i8"), ("count", "<i8"), ("n_speed", "<i8"),
                             ("sum_speed", "<f8"), ("sum_lat", "<f8"), ("sum_lon", "<f8"), ("reserved", "<i8")])
@@ -220,6 +229,16 @@ SIGNATURES = {
                                        _P(c_vp), _P(c_vp)]),
     "hm_selftest_tile_features_near": (c_i32, [_P(HmGeojsonCfg), c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "hm_selftest_position_features_near": (c_i32, [_P(HmPositionDocCfg), c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "hm_points_in_zones": (c_i32, [_P(HmZones), c_vp, c_vp, c_i64, c_i32, c_i32, c_vp, c_vp]),
+    "hm_selftest_points_in_zones": (c_i32, [_P(HmZones), c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "hm_positions_within": (c_i32, [c_vp, _P(HmZones), c_i64, c_i32, c_vp, _P(c_vp), _P(c_vp), _P(c_i64)]),
+    "hm_window_within": (c_i32, [c_vp, c_i64, c_i32, _P(HmZones), c_i32, c_vp, _P(c_vp), _P(c_vp), _P(c_i64)]),
+    "hm_positions_geojson_within": (c_i32, [c_vp, _P(HmPositionDocCfg), c_i32, _P(c_vp), _P(c_vp), _P(c_i64), _P(c_vp), _P(HmZones)]),
+    "hm_window_geojson_within": (c_i32, [c_vp, c_i64, c_i32, _P(HmGeojsonCfg), c_i32, _P(c_vp), _P(c_vp), _P(c_i64), _P(c_vp),
+                                         _P(HmZones)]),
+    "hm_selftest_positions_within": (c_i32, [_P(HmZones), c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, _P(c_i64)]),
+    "hm_selftest_tiles_within": (c_i32, [_P(HmZones), c_vp, c_i64, c_vp, c_vp, c_vp, _P(c_i64)]),
+    "hm_within_info": (c_i32, [c_vp, c_vp, c_i32]),
     "hm_selftest_float_repr_host": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "hm_selftest_float_repr_device": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32]),
     "hm_abi_version": (c_i32, []),
@@ -797,3 +816,97 @@ def position_recs_at(p, n, copy=True):
         return np.zeros(0, POSITION_REC_DTYPE)
     recs = np.ctypeslib.as_array(ctypes.cast(p, _P(ctypes.c_uint8)), shape=(n * POSITION_REC_DTYPE.itemsize,)).view(POSITION_REC_DTYPE)
     return recs.copy() if copy else recs
+
+
+# ---- polygon geofences (csrc/k_within.h) ----
+HM_ZONES_MAX = 4096
+HM_ZONE_VERTS_MAX = 65536
+
+
+class Zones:
+    """A zone set as the library takes it: zone z is the rings zone_rings[z] .. zone_rings[z + 1] - 1, ring r the vertices
+    ring_verts[r] .. ring_verts[r + 1] - 1 of (lat, lon) in degrees, without the repeated closing vertex.  Validity is
+    the library's to judge (HM_E_INVALID)."""
+
+    def __init__(self, zone_rings, ring_verts, lat, lon):
+        self.zone_rings = np.ascontiguousarray(zone_rings, dtype=np.int32).reshape(-1)
+        self.ring_verts = np.ascontiguousarray(ring_verts, dtype=np.int32).reshape(-1)
+        self.lat = np.ascontiguousarray(lat, dtype=np.float64).reshape(-1)
+        self.lon = np.ascontiguousarray(lon, dtype=np.float64).reshape(-1)
+
+    @property
+    def n_zones(self):
+        return max(self.zone_rings.size - 1, 0)
+
+    @classmethod
+    def from_rings(cls, zones):
+        """zones: a list of zones, each a list of rings, each a list of (lat, lon) vertices"""
+        zr, rv, la, lo = [0], [0], [], []
+        for rings in zones:
+            for ring in rings:
+                la += [float(v[0]) for v in ring]
+                lo += [float(v[1]) for v in ring]
+                rv.append(len(la))
+            zr.append(len(rv) - 1)
+        return cls(zr, rv, la, lo)
+
+    def rings(self, z):
+        """zone z as a list of (lat, lon) arrays, one pair per ring"""
+        return [(self.lat[self.ring_verts[r]:self.ring_verts[r + 1]], self.lon[self.ring_verts[r]:self.ring_verts[r + 1]])
+                for r in range(int(self.zone_rings[z]), int(self.zone_rings[z + 1]))]
+
+
+def zones_struct(zones):
+    """(hm_zones, what must stay alive) of a Zones"""
+    p = (lambda a: ptr(a) if a.size else None)
+    return HmZones(n_zones=zones.n_zones, zone_rings=p(zones.zone_rings), ring_verts=p(zones.ring_verts), lat=p(zones.lat),
+                   lon=p(zones.lon)), zones
+
+
+def points_in_zones_selftest(zones, lat, lon, device=None):
+    """(first zone int32 or -1, hits uint32) of every (lat[i], lon[i]): host execution of the kernels' predicate (no GPU),
+    or on GPU `device` (hm_points_in_zones)."""
+    lib = load()
+    lat = np.ascontiguousarray(lat, dtype=np.float64).reshape(-1)
+    lon = np.ascontiguousarray(lon, dtype=np.float64).reshape(-1)
+    assert lat.size == lon.size
+    z, keep = zones_struct(zones)
+    first, hits = np.zeros(lat.size, np.int32), np.zeros(lat.size, np.uint32)
+    p = (lambda a: ptr(a) if a.size else None)
+    if device is None:
+        check(lib.hm_selftest_points_in_zones(ctypes.byref(z), p(lat), p(lon), lat.size, p(first), p(hits)), None,
+              "hm_selftest_points_in_zones")
+    else:
+        check(lib.hm_points_in_zones(ctypes.byref(z), p(lat), p(lon), lat.size, HM_MEM_HOST, int(device), p(first), p(hits)), None,
+              "hm_points_in_zones")
+    return first, hits
+
+
+def _within_selftest(fn, dtype, zones, recs, *lead):
+    lib = load()
+    recs = np.ascontiguousarray(recs, dtype=dtype)
+    z, keep = zones_struct(zones)
+    room = max(recs.size, 1)
+    out, zone, tot, n = np.zeros(room, dtype), np.zeros(room, np.int32), np.zeros(max(zones.n_zones, 1), ZONE_REC_DTYPE), c_i64()
+    check(getattr(lib, fn)(ctypes.byref(z), *lead, ptr(recs) if recs.size else None, recs.size, ptr(tot), ptr(out), ptr(zone),
+                           ctypes.byref(n)), None, fn)
+    return out[:n.value].copy(), zone[:n.value].copy(), tot[:zones.n_zones].copy()
+
+
+def positions_within_selftest(zones, recs, since_us=None):
+    """Host execution of the within query (no GPU) on POSITION_REC_DTYPE records: (the records with ts_us >= since_us in at
+    least one zone, in input order; their labels int32; the zones' totals ZONE_REC_DTYPE)."""
+    return _within_selftest("hm_selftest_positions_within", POSITION_REC_DTYPE, zones, recs, INT64_MIN if since_us is None else int(since_us))
+
+
+def tiles_within_selftest(zones, recs):
+    """The same on STATE_REC_DTYPE records by their centroid (sum_lat / count, sum_lon / count)."""
+    return _within_selftest("hm_selftest_tiles_within", STATE_REC_DTYPE, zones, recs)
+
+
+def int32s_at(p, n, copy=True):
+    """n int32 at host pointer p (a copy, or a view of the library's buffer)."""
+    if n == 0:
+        return np.zeros(0, np.int32)
+    a = np.ctypeslib.as_array(ctypes.cast(p, _P(ctypes.c_int32)), shape=(n,))
+    return a.copy() if copy else a

@@ -824,6 +824,89 @@ class HeatmapEngine:
         return {"scanned": v[0], "kept_since": v[1], "nan": v[2], "within": v[3], "returned": v[4], "passes": v[5],
                 "emit_us": v[6], "select_us": v[7]}
 
+    # ---- polygon geofences: the vehicles / tiles inside zones (hm_*_within; csrc/k_within.h) ----
+    def positions_within(self, zones, since_us=None, records=True, copy=True):
+        """The vehicles of the positions state inside the zones of a _lib.Zones (readside.zones_from_geojson), among those
+        with ts_us >= since_us (None: all): (records POSITION_REC_DTYPE in no particular order, labels int32 -- the
+        lowest-index zone that contains each --, totals ZONE_REC_DTYPE: per zone n = count = its vehicles, newest_us
+        their newest ts_us; a vehicle counts in every zone that contains it).  Membership (readside.points_in_zones, no
+        tolerance), labels, compaction and totals on the GPU in one scan (hm_positions_within).  records=False: totals
+        only (None, None, totals).  copy=False: views of the library's pinned buffers, valid until the next call."""
+        z, keep = _lib.zones_struct(zones)
+        since = _lib.INT64_MIN if since_us is None else int(since_us)
+        tot = np.zeros(max(zones.n_zones, 1), _lib.ZONE_REC_DTYPE)
+        p, pz, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        check(self._lib.hm_positions_within(self._ctx, ctypes.byref(z), since, HM_MEM_HOST, _lib.ptr(tot),
+                                            ctypes.byref(p) if records else None, ctypes.byref(pz) if records else None,
+                                            ctypes.byref(n)), self._ctx, "hm_positions_within")
+        tot = tot[:zones.n_zones]
+        if not records:
+            return None, None, tot
+        return _lib.position_recs_at(p, n.value, copy), _lib.int32s_at(pz, n.value, copy), tot
+
+    def window_within(self, zones, window_start_us=None, res=None, records=True, copy=True):
+        """The tiles of one live window (None: the newest) at resolution res <= h3_res (None: h3_res) whose centroid
+        (sum_lat / count, sum_lon / count, as window_tiles) is inside the zones: (records STATE_REC_DTYPE, labels int32,
+        totals ZONE_REC_DTYPE: per zone n = its tiles, count / n_speed / sum_speed their sums), as positions_within
+        (hm_window_within).  A window that is not live gives no record and zero totals."""
+        res = self.h3_res if res is None else int(res)
+        if window_start_us is None:
+            ws, _ = self.live_windows()
+            window_start_us = ws[-1] if ws.size else 0
+        z, keep = _lib.zones_struct(zones)
+        tot = np.zeros(max(zones.n_zones, 1), _lib.ZONE_REC_DTYPE)
+        p, pz, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        check(self._lib.hm_window_within(self._ctx, int(window_start_us), res, ctypes.byref(z), HM_MEM_HOST, _lib.ptr(tot),
+                                         ctypes.byref(p) if records else None, ctypes.byref(pz) if records else None,
+                                         ctypes.byref(n)), self._ctx, "hm_window_within")
+        tot = tot[:zones.n_zones]
+        if not records:
+            return None, None, tot
+        return _lib.state_recs_at(p, n.value, copy), _lib.int32s_at(pz, n.value, copy), tot
+
+    def positions_within_geojson(self, zones, tz=None, copy=True, with_records=False):
+        """The body of a /api/positions/within route: json.dumps(readside.positions_within_from_engine(...), separators=
+        (",", ":")) as bytes, feature order apart -- positions_geojson's features of the vehicles in at least one zone,
+        the records never leaving the device between the scan and the encoder (hm_positions_geojson_within).  tz / copy /
+        with_records as positions_geojson."""
+        cfg, keep = _lib.bucket_cfg(self.positions_buckets(), tz)
+        z, zkeep = _lib.zones_struct(zones)
+        pb, po, pr, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        check(self._lib.hm_positions_geojson_within(self._ctx, ctypes.byref(cfg), HM_MEM_HOST, ctypes.byref(pb), ctypes.byref(po),
+                                                    ctypes.byref(n), ctypes.byref(pr) if with_records else None, ctypes.byref(z)),
+              self._ctx, "hm_positions_geojson_within")
+        body = self._geojson_body(pb, po, n.value, copy)
+        if not with_records:
+            return body
+        offs = np.ctypeslib.as_array(ctypes.cast(po, ctypes.POINTER(ctypes.c_int64)), shape=(n.value + 1,)).copy()
+        return body, _lib.position_recs_at(pr, n.value), offs
+
+    def window_within_geojson(self, zones, window_start_us=None, res=None, tz=None, copy=True, with_records=False):
+        """The body of a /api/tiles/within route: json.dumps(readside.tiles_within_from_engine(...), separators=(",", ":"))
+        as bytes, feature order apart -- window_geojson's features of the tiles whose centroid is in at least one zone,
+        rolled up, filtered and encoded on the GPU in one call (hm_window_geojson_within)."""
+        res = self.h3_res if res is None else int(res)
+        if window_start_us is None:
+            ws, _ = self.live_windows()
+            window_start_us = ws[-1] if ws.size else 0
+        window_start_us = int(window_start_us)
+        cfg, keep = _lib.geojson_cfg(_lib.wall_iso(window_start_us, tz), _lib.wall_iso(window_start_us + self.tile_us, tz))
+        z, zkeep = _lib.zones_struct(zones)
+        pb, po, pr, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        check(self._lib.hm_window_geojson_within(self._ctx, window_start_us, res, ctypes.byref(cfg), HM_MEM_HOST, ctypes.byref(pb),
+                                                 ctypes.byref(po), ctypes.byref(n), ctypes.byref(pr) if with_records else None,
+                                                 ctypes.byref(z)), self._ctx, "hm_window_geojson_within")
+        body = self._geojson_body(pb, po, n.value, copy)
+        if not with_records:
+            return body
+        offs = np.ctypeslib.as_array(ctypes.cast(po, ctypes.POINTER(ctypes.c_int64)), shape=(n.value + 1,)).copy()
+        return body, _lib.state_recs_at(pr, n.value), offs
+
+    def within_info(self):
+        v = (ctypes.c_int64 * 6)()
+        check(self._lib.hm_within_info(self._ctx, v, 6), self._ctx, "hm_within_info")
+        return {"scanned": v[0], "kept_since": v[1], "in_zone": v[2], "zones": v[3], "vertices": v[4], "scan_us": v[5]}
+
     def encode_tile_updates_device(self, city, ttl_minutes):
         """The same, left on the device: (device pointer of the bytes, of the offsets, n statements)."""
         n = ctypes.c_int64()

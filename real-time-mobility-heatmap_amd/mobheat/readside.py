@@ -532,3 +532,130 @@ def tiles_near_body(engine, lat, lon, max_distance_m=float("inf"), k=TOP_MAX, re
     """The response body of a /api/tiles/near route as bytes: json.dumps(tiles_near_from_engine(...), separators=(",", ":")),
     rolled up, ranked and encoded on the GPU (HeatmapEngine.window_near_geojson)."""
     return engine.window_near_geojson(lat, lon, max_distance_m, k, None, res, tz)
+
+
+# ---- polygon geofences: what is inside zones (HeatmapEngine.positions_within / window_within, csrc/k_within.h) ----
+def zones_from_geojson(obj):
+    """The _lib.Zones of a GeoJSON Polygon, MultiPolygon, Feature or FeatureCollection (a dict, or its JSON text): one zone
+    per Polygon, one zone of all its rings per MultiPolygon, in document order; positions are [lon, lat] (anything after
+    them is ignored); a closed ring loses its last vertex.  ValueError for any other geometry.  The coordinates are the
+    library's to validate (HM_E_INVALID)."""
+    import json
+    if isinstance(obj, (str, bytes)):
+        obj = json.loads(obj)
+
+    def ring(r):
+        r = [(float(p[1]), float(p[0])) for p in r]
+        return r[:-1] if len(r) > 1 and r[0] == r[-1] else r
+
+    def zones(g):
+        t = g.get("type")
+        if t == "FeatureCollection":
+            return [z for f in g["features"] for z in zones(f)]
+        if t == "Feature":
+            return zones(g["geometry"])
+        if t == "Polygon":
+            return [[ring(r) for r in g["coordinates"]]]
+        if t == "MultiPolygon":
+            return [[ring(r) for poly in g["coordinates"] for r in poly]]
+        raise ValueError(f"zones_from_geojson: a {t!r} is no Polygon, MultiPolygon, Feature or FeatureCollection")
+    return _lib.Zones.from_rings(zones(obj))
+
+
+def zones_to_geojson(zones):
+    """A FeatureCollection of one Polygon Feature per zone (its rings closed again, in the zone's order: a zone made from
+    a MultiPolygon comes back as the Polygon of all its rings, which has the same members under the even-odd rule)."""
+    feats = []
+    for z in range(zones.n_zones):
+        rings_ = []
+        for la, lo in zones.rings(z):
+            r = [[float(x), float(y)] for y, x in zip(la, lo)]
+            rings_.append(r + [r[0]])
+        feats.append({"type": "Feature", "geometry": {"type": "Polygon", "coordinates": rings_}, "properties": {"zone": z}})
+    return {"type": "FeatureCollection", "features": feats}
+
+
+def points_in_zones(zones, lat, lon, block=1 << 21):
+    """(first zone int32 or -1, hits uint32) of every point: the comparison form of the device's membership rule
+    (include/mobheat.h), the same binary64 operations in the same order, one rounding each, in numpy -- per zone a points x
+    edges matrix of the crossing predicate (in blocks of about `block` elements), a point is in the zone iff its row has
+    an odd number of crossings."""
+    lat = np.ascontiguousarray(lat, dtype=np.float64).reshape(-1)
+    lon = np.ascontiguousarray(lon, dtype=np.float64).reshape(-1)
+    first = np.full(lat.size, -1, np.int32)
+    hits = np.zeros(lat.size, np.uint32)
+    for z in range(zones.n_zones):
+        a_lat, a_lon, b_lat, b_lon = [], [], [], []
+        for la, lo in zones.rings(z):
+            a_lat.append(la)
+            a_lon.append(lo)
+            b_lat.append(np.roll(la, -1))
+            b_lon.append(np.roll(lo, -1))
+        a_lat, a_lon, b_lat, b_lon = (np.concatenate(x) for x in (a_lat, a_lon, b_lat, b_lon))
+        swap = a_lat > b_lat   # the canonical direction: a.lat < b.lat (a horizontal edge is never crossed: its range is empty)
+        a_lat, b_lat = np.where(swap, b_lat, a_lat), np.where(swap, a_lat, b_lat)
+        a_lon, b_lon = np.where(swap, b_lon, a_lon), np.where(swap, a_lon, b_lon)
+        w, h = b_lon - a_lon, b_lat - a_lat
+        step = max(int(block) // max(a_lat.size, 1), 1)
+        inside = np.zeros(lat.size, bool)
+        with np.errstate(invalid="ignore", over="ignore"):
+            for i in range(0, lat.size, step):
+                la, lo = lat[i:i + step, None], lon[i:i + step, None]
+                straddles = (a_lat[None, :] <= la) & (la < b_lat[None, :])
+                crossed = straddles & (w[None, :] * (la - a_lat[None, :]) > (lo - a_lon[None, :]) * h[None, :])
+                inside[i:i + step] = (np.count_nonzero(crossed, axis=1) & 1) == 1
+        first[inside & (first < 0)] = z
+        hits += inside.astype(np.uint32)
+    return first, hits
+
+
+def zone_totals_of(zones, lat, lon, keep=None, count=None, n_speed=None, sum_speed=None, ts_us=None):
+    """(inside: zones x points bool) and the ZONE_REC_DTYPE totals of candidate points by points_in_zones, one zone at a
+    time: ts_us given -- positions (n = count = the members, newest_us their newest); else tiles (the members' sums)."""
+    lat, lon = np.asarray(lat, np.float64), np.asarray(lon, np.float64)
+    keep = np.ones(lat.size, bool) if keep is None else np.asarray(keep, bool)
+    tot = np.zeros(zones.n_zones, _lib.ZONE_REC_DTYPE)
+    inside = np.zeros((zones.n_zones, lat.size), bool)
+    for z in range(zones.n_zones):
+        one = _lib.Zones.from_rings([[list(zip(la, lo)) for la, lo in zones.rings(z)]])
+        inside[z] = (points_in_zones(one, lat, lon)[1] == 1) & keep
+        m = inside[z]
+        tot["n"][z] = int(m.sum())
+        if ts_us is not None:
+            tot["count"][z] = tot["n"][z]
+            tot["newest_us"][z] = int(np.asarray(ts_us)[m].max()) if m.any() else _lib.INT64_MIN
+        else:
+            tot["count"][z] = int(np.asarray(count)[m].sum())
+            tot["n_speed"][z] = int(np.asarray(n_speed)[m].sum())
+            tot["sum_speed"][z] = float(np.asarray(sum_speed, np.float64)[m].sum())
+    return inside, tot
+
+
+def positions_within_from_engine(engine, zones, tz=None):
+    """The FeatureCollection a /api/positions/within route returns: positions_latest_from_engine's features whose point is
+    in at least one zone, filtered here in Python (points_in_zones).  The comparison form of positions_within_body."""
+    f = positions_latest_from_engine(engine, tz)["features"]
+    _, hits = points_in_zones(zones, [x["geometry"]["coordinates"][1] for x in f], [x["geometry"]["coordinates"][0] for x in f])
+    return {"type": "FeatureCollection", "features": [x for x, k in zip(f, hits) if k]}
+
+
+def tiles_within_from_engine(engine, zones, res=None, city="boston", tz=None):
+    """The FeatureCollection a /api/tiles/within route returns: tiles_latest_from_engine's features of the newest live
+    window at resolution res whose tile document's centroid is in at least one zone, filtered here in Python.  The
+    comparison form of tiles_within_body."""
+    docs = tile_docs_from_engine(engine, res, city, tz)
+    f = tiles_latest_collection(docs, engine.device)["features"]
+    _, hits = points_in_zones(zones, [d["centroid"]["coordinates"][1] for d in docs], [d["centroid"]["coordinates"][0] for d in docs])
+    return {"type": "FeatureCollection", "features": [x for x, k in zip(f, hits) if k]}
+
+
+def positions_within_body(engine, zones, tz=None):
+    """The response body of a /api/positions/within route as bytes: json.dumps(positions_within_from_engine(...),
+    separators=(",", ":")), feature order apart, filtered and encoded on the GPU (HeatmapEngine.positions_within_geojson)."""
+    return engine.positions_within_geojson(zones, tz)
+
+
+def tiles_within_body(engine, zones, res=None, tz=None):
+    """The response body of a /api/tiles/within route as bytes: json.dumps(tiles_within_from_engine(...), separators=(",",
+    ":")), feature order apart, rolled up, filtered and encoded on the GPU (HeatmapEngine.window_within_geojson)."""
+    return engine.window_within_geojson(zones, None, res, tz)
