@@ -884,6 +884,14 @@ int hm_selftest_tiles_within(const hm_zones *zones, const hm_state_rec *recs, in
  * events around it).  All 0 before the first call. */
 int hm_within_info(const hm_ctx *ctx, int64_t *v, int32_t n);
 
+/* Tests: MOBHEAT_TEST_READ_GRID=<G>, read at hm_create (and by every hm_cells_in_view / hm_points_in_zones on a device),
+ * runs the streaming kernels of the read side (view, roll-up, density, within, raster, GeoJSON, positions export), of the
+ * state dump and of the sink on at most G workgroups, so that a few thousand items are several grid-stride iterations
+ * of every workgroup; 0 or unset: every grid as without it.  *launches_lowered: the launches whose grid it lowered since
+ * the context was created; *least_iterations / *most_iterations: the fewest / most iterations ceil(items / (items per
+ * workgroup iteration * G)) among them (0, 0 when none).  ctx NULL: the same of the process's context-free calls. */
+int hm_test_read_grid_info(const hm_ctx *ctx, int64_t *launches_lowered, int64_t *least_iterations, int64_t *most_iterations);
+
 /* json.dumps(x) of n doubles -- CPython's float.__repr__, NaN / Infinity / -Infinity for the non-finite -- as the GeoJSON
  * encoders write them (csrc/float_repr.h), executed on the host and on GPU `device` (test entry points): value i's
  * len[i] <= 24 bytes at text[24 i]. */

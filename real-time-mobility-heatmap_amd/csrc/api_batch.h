@@ -152,6 +152,9 @@ int hm_create(const hm_config *cfg, hm_ctx **out) {
     // MOBHEAT_TEST_TOP_GRID (tests): at most that many workgroups in the top's streaming kernels (keys, passes,
     // compaction), so that a few thousand records are several grid-stride iterations of every workgroup (top_on_device)
     if (const char *m = getenv("MOBHEAT_TEST_TOP_GRID")) ctx->top.test_grid = std::max(0, atoi(m));
+    // MOBHEAT_TEST_READ_GRID (tests): at most that many workgroups in the streaming kernels of the rest of the read side
+    // (view, roll-up, density, within, raster, GeoJSON, positions export, state dump) and of the sink (read_grid)
+    if (const char *m = getenv("MOBHEAT_TEST_READ_GRID")) ctx->read_grid.g = std::max(0, atoi(m));
     // the registry, its census and the batch statistics side by side (one reset, one readback after k_ingest)
     if (hipMalloc(&ctx->d_wreg, REG_BLOCK_BYTES) != hipSuccess || !(ctx->d_wcount = ctx->d_wreg + WREG_SLOTS + 1) ||
         !(ctx->d_st = (DevStats *)(ctx->d_wreg + 2 * (WREG_SLOTS + 1))) ||

@@ -54,15 +54,15 @@ static int density_on_device(hm_ctx *ctx, int32_t res, int64_t since_us, const h
     HIPCHK(ctx, hipMemsetAsync(tab, 0, (size_t)nslots * sizeof(GrowRec), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(words, 0, DW_WORDS * 8, ctx->stream));
     // one group-by workgroup per CU (its LDS table takes most of a CU's LDS), looping over the slots
-    const int groups_grid = grid_for(cap, RU_THREADS * DUMP_PER, std::max(ctx->n_cus, 1));
+    const int groups_grid = read_grid(ctx->read_grid, cap, RU_THREADS * DUMP_PER, std::max(ctx->n_cus, 1));
     HIPCHK(ctx, hipEventRecord(D.ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_density_cells, dim3(grid_for(cap, 256, 256 * 32)), dim3(256), 0, ctx->stream, (const PosSlot *)P.tab, cap,
+    hipLaunchKernelGGL(k_density_cells, dim3(read_grid(ctx->read_grid, cap, 256, 256 * 32)), dim3(256), 0, ctx->stream, (const PosSlot *)P.tab, cap,
                        (int)res, (long long)since_us, (uint64_t *)D.cell_of.p, (unsigned int *)D.slow.p, words + DW_SLOW);
     hipLaunchKernelGGL(k_density_exact, dim3(256), dim3(256), 0, ctx->stream, (const PosSlot *)P.tab, (int)res, (uint64_t *)D.cell_of.p,
                        (const unsigned int *)D.slow.p, (const unsigned long long *)(words + DW_SLOW));
     hipLaunchKernelGGL(k_density_group, dim3(groups_grid), dim3(RU_THREADS), 0, ctx->stream, (const PosSlot *)P.tab, cap,
                        (const uint64_t *)D.cell_of.p, tab, (unsigned long long)(nslots - 1), words);
-    hipLaunchKernelGGL(k_density_emit, dim3(grid_for(nslots, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, (const GrowRec *)tab, nslots,
+    hipLaunchKernelGGL(k_density_emit, dim3(read_grid(ctx->read_grid, nslots, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, (const GrowRec *)tab, nslots,
                        (GrowRec *)D.out.p, bound, words + DW_OUT);
     HIPCHK(ctx, hipEventRecord(D.ev[1], ctx->stream));
     HIPCHK(ctx, hipGetLastError());
@@ -81,7 +81,7 @@ static int density_on_device(hm_ctx *ctx, int32_t res, int64_t since_us, const h
     if (view && m > 0) {   // (the view's validity is the caller's check)
         const ViewPoles &poles = view_poles();
         HIPCHK(ctx, hipEventRecord(D.ev[2], ctx->stream));
-        hipLaunchKernelGGL(k_view_tiles, dim3(grid_for(m, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, out, m, poles.north[res],
+        hipLaunchKernelGGL(k_view_tiles, dim3(read_grid(ctx->read_grid, m, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, out, m, poles.north[res],
                            poles.south[res], *view, (GrowRec *)D.vout.p, words + DW_VIEW);
         HIPCHK(ctx, hipEventRecord(D.ev[3], ctx->stream));
         HIPCHK(ctx, hipGetLastError());

@@ -43,7 +43,7 @@ static void gj_scan(hm_ctx *ctx, int64_t n) {
     hipLaunchKernelGGL(k_scan_blocks, dim3(nb), dim3(1024), 0, ctx->stream, (const unsigned *)G.sizes.p, m, off, (unsigned *)G.btot.p);
     hipLaunchKernelGGL(k_cp_scan, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned *)G.btot.p, nb, (unsigned long long *)G.boff.p,
                        off + m);
-    hipLaunchKernelGGL(k_scan_add, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, off, m, (const unsigned long long *)G.boff.p);
+    hipLaunchKernelGGL(k_scan_add, dim3(read_grid(ctx->read_grid, m, 256)), dim3(256), 0, ctx->stream, off, m, (const unsigned long long *)G.boff.p);
 }
 // the body without a feature
 static int gj_empty(hm_ctx *ctx) {
@@ -101,7 +101,7 @@ static int gj_tiles(hm_ctx *ctx, const GjTexts &T, const GrowRec *recs, int64_t 
     double *vlat = (double *)G.verts.p, *vlng = vlat + 10 * n;
     HIPCHK(ctx, hipMemsetAsync(words, 0, GJW_WORDS * 8, ctx->stream));
     HIPCHK(ctx, hipEventRecord(G.ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_gj_tile_sizes, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, T, recs, n, vlat, vlng, (int *)G.vn.p,
+    hipLaunchKernelGGL(k_gj_tile_sizes, dim3(read_grid(ctx->read_grid, n, 256)), dim3(256), 0, ctx->stream, T, recs, n, vlat, vlng, (int *)G.vn.p,
                        (unsigned *)G.sizes.p, words, dist_m);
     HIPCHK(ctx, hipEventRecord(G.ev[1], ctx->stream));
     gj_scan(ctx, n);
@@ -117,7 +117,7 @@ static int gj_tiles(hm_ctx *ctx, const GjTexts &T, const GrowRec *recs, int64_t 
     if ((rc = ensure(ctx, G.bytes, (size_t)body_len + 16))) return rc;
     const size_t lds = (size_t)GJ_THREADS * ((longest + 15) & ~15ull) + 64;   // (<= 64 x 912 + 64 B: below the 64-KB default)
     HIPCHK(ctx, hipEventRecord(G.ev[2], ctx->stream));
-    hipLaunchKernelGGL(k_gj_tile_write, dim3(grid_for(n, GJ_THREADS)), dim3(GJ_THREADS), lds, ctx->stream, T, recs, n,
+    hipLaunchKernelGGL(k_gj_tile_write, dim3(read_grid(ctx->read_grid, n, GJ_THREADS)), dim3(GJ_THREADS), lds, ctx->stream, T, recs, n,
                        (const double *)vlat, (const double *)vlng, (const int *)G.vn.p, (const unsigned long long *)G.off.p,
                        (uint8_t *)G.bytes.p, dist_m);
     HIPCHK(ctx, hipEventRecord(G.ev[3], ctx->stream));
@@ -219,10 +219,10 @@ int hm_positions_buckets(hm_ctx *ctx, int64_t *bucket_ids, int64_t cap, int64_t 
     const unsigned long long scap = next_pow2((unsigned long long)std::max<int64_t>(2 * P.keys, 1024));
     if ((rc = ensure(ctx, G.bset, scap * 8)) || (rc = ensure(ctx, G.blist, (size_t)P.keys * 8))) return rc;
     unsigned long long *w = (unsigned long long *)G.words.p + GJW_BUCKETS;
-    hipLaunchKernelGGL(k_fill_i64, dim3(grid_for((int64_t)scap, 256)), dim3(256), 0, ctx->stream, (long long *)G.bset.p, (int64_t)scap,
+    hipLaunchKernelGGL(k_fill_i64, dim3(read_grid(ctx->read_grid, (int64_t)scap, 256)), dim3(256), 0, ctx->stream, (long long *)G.bset.p, (int64_t)scap,
                        (long long)INT64_MIN);
     HIPCHK(ctx, hipMemsetAsync(w, 0, 8, ctx->stream));
-    hipLaunchKernelGGL(k_gj_pos_buckets, dim3(grid_for((int64_t)P.cap, 256)), dim3(256), 0, ctx->stream, (const PosSlot *)P.tab,
+    hipLaunchKernelGGL(k_gj_pos_buckets, dim3(read_grid(ctx->read_grid, (int64_t)P.cap, 256)), dim3(256), 0, ctx->stream, (const PosSlot *)P.tab,
                        (int64_t)P.cap, (long long *)G.bset.p, scap - 1, (long long *)G.blist.p, w);
     HIPCHK(ctx, hipGetLastError());
     unsigned long long k = 0;
@@ -285,12 +285,12 @@ static int gj_positions(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t
     // the state's records in feature order (k_pos_emit's compaction, into a buffer of this call's own)
     if (given) {   // (nothing to emit: the caller's records)
     } else if (!view) {
-        hipLaunchKernelGGL(k_pos_emit, dim3(grid_for((int64_t)P.cap, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, (const PosSlot *)P.tab,
+        hipLaunchKernelGGL(k_pos_emit, dim3(read_grid(ctx->read_grid, (int64_t)P.cap, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, (const PosSlot *)P.tab,
                            (int64_t)P.cap, (hm_position_rec *)G.precs.p, m, words + GJW_OUT);
     } else {   // the same compaction with the point test; the features run over what it kept
         unsigned long long kept = 0;
         HIPCHK(ctx, hipEventRecord(G.vev[0], ctx->stream));
-        hipLaunchKernelGGL(k_pos_emit_view, dim3(grid_for((int64_t)P.cap, 256 * DUMP_PER)), dim3(256), 0, ctx->stream,
+        hipLaunchKernelGGL(k_pos_emit_view, dim3(read_grid(ctx->read_grid, (int64_t)P.cap, 256 * DUMP_PER)), dim3(256), 0, ctx->stream,
                            (const PosSlot *)P.tab, (int64_t)P.cap, *view, (hm_position_rec *)G.precs.p, m, words + GJW_OUT);
         HIPCHK(ctx, hipEventRecord(G.vev[1], ctx->stream));
         HIPCHK(ctx, hipGetLastError());
@@ -319,7 +319,7 @@ static int gj_positions(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t
     F.bucket_off = F.bucket_id + nb;
     const hm_position_rec *d = given ? given->recs : (const hm_position_rec *)G.precs.p;
     HIPCHK(ctx, hipEventRecord(G.ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_gj_pos_sizes, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, F, d, m, (unsigned *)G.sizes.p, words, dist_m);
+    hipLaunchKernelGGL(k_gj_pos_sizes, dim3(read_grid(ctx->read_grid, m, 256)), dim3(256), 0, ctx->stream, F, d, m, (unsigned *)G.sizes.p, words, dist_m);
     HIPCHK(ctx, hipEventRecord(G.ev[1], ctx->stream));
     gj_scan(ctx, m);
     HIPCHK(ctx, hipGetLastError());
@@ -334,7 +334,7 @@ static int gj_positions(hm_ctx *ctx, const hm_position_doc_cfg *buckets, int32_t
     const int64_t body_len = (int64_t)total + 1;
     if ((rc = ensure(ctx, G.bytes, (size_t)body_len + 16))) return rc;
     HIPCHK(ctx, hipEventRecord(G.ev[2], ctx->stream));
-    hipLaunchKernelGGL(k_gj_pos_write, dim3(grid_for(m, 256)), dim3(256), 0, ctx->stream, F, d, m, (const unsigned long long *)G.off.p,
+    hipLaunchKernelGGL(k_gj_pos_write, dim3(read_grid(ctx->read_grid, m, 256)), dim3(256), 0, ctx->stream, F, d, m, (const unsigned long long *)G.off.p,
                        (uint8_t *)G.bytes.p, dist_m);
     HIPCHK(ctx, hipEventRecord(G.ev[3], ctx->stream));
     HIPCHK(ctx, hipGetLastError());

@@ -296,7 +296,7 @@ int hm_positions_export(hm_ctx *ctx, int32_t out_memory, const hm_position_rec *
     if ((rc = ensure(ctx, P.x_recs, (size_t)std::max<int64_t>(m, 1) * sizeof(hm_position_rec)))) return rc;
     HIPCHK(ctx, hipMemsetAsync(P.words + PW_OUT, 0, 8, ctx->stream));
     if (P.tab) {
-        hipLaunchKernelGGL(k_pos_emit, dim3(grid_for((int64_t)P.cap, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, (const PosSlot *)P.tab,
+        hipLaunchKernelGGL(k_pos_emit, dim3(read_grid(ctx->read_grid, (int64_t)P.cap, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, (const PosSlot *)P.tab,
                            (int64_t)P.cap, (hm_position_rec *)P.x_recs.p, m, P.words + PW_OUT);
         HIPCHK(ctx, hipGetLastError());
     }

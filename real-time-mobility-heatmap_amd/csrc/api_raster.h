@@ -52,7 +52,7 @@ static int raster_from_table(hm_ctx *ctx, const GrowRec *tab, int64_t nslots, in
         const unsigned long long mask = (unsigned long long)(nslots - 1);
         const int64_t nunits = (int64_t)rows * ((cols + 63) / 64);   // a wave each, four to a workgroup
         HIPCHK(ctx, hipEventRecord(R.ev[0], ctx->stream));
-        hipLaunchKernelGGL(k_raster, dim3(grid_for(nunits, 4, 256 * 32)), dim3(256), 0, ctx->stream, (const double *)R.lat.p, (int)rows,
+        hipLaunchKernelGGL(k_raster, dim3(read_grid(ctx->read_grid, nunits, 4, 256 * 32)), dim3(256), 0, ctx->stream, (const double *)R.lat.p, (int)rows,
                            (const double *)R.lon.p, (int)cols, (int)res, tab, mask, thr, d_counts, d_classes, (unsigned int *)R.slow.p,
                            n_slow);
         hipLaunchKernelGGL(k_raster_exact, dim3(256), dim3(256), 0, ctx->stream, (const double *)R.lat.p, (const double *)R.lon.p,

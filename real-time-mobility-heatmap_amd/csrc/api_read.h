@@ -49,10 +49,10 @@ static int rollup_on_device(hm_ctx *ctx, int64_t window_start_us, int32_t res, c
     HIPCHK(ctx, hipMemsetAsync(words, 0, 16, ctx->stream));
     const GenDesc d = gen_desc(*gen);
     // one workgroup per CU (its LDS table takes most of a CU's LDS), looping over the table
-    const int grid = grid_for(int64_t(1) << gen->log2cap, RU_THREADS * DUMP_PER, std::max(ctx->n_cus, 1));
+    const int grid = read_grid(ctx->read_grid, int64_t(1) << gen->log2cap, RU_THREADS * DUMP_PER, std::max(ctx->n_cus, 1));
     hipLaunchKernelGGL(k_rollup, dim3(grid), dim3(RU_THREADS), 0, ctx->stream, d, (int)res, (GrowRec *)ctx->ru_tab.p,
                        (unsigned long long)(nslots - 1), words + 1);
-    hipLaunchKernelGGL(k_rollup_emit, dim3(grid_for(nslots, 256 * DUMP_PER)), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL(k_rollup_emit, dim3(read_grid(ctx->read_grid, nslots, 256 * DUMP_PER)), dim3(256), 0, ctx->stream,
                        (const GrowRec *)ctx->ru_tab.p, nslots, window_start_us, (GrowRec *)ctx->ru_out.p, bound, words);
     HIPCHK(ctx, hipGetLastError());
     unsigned long long got[2] = {0, 0};

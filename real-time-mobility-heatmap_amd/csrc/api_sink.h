@@ -138,7 +138,7 @@ int hm_encode_tile_updates(hm_ctx *ctx, const hm_tile_doc_cfg *cfg, int32_t out_
     int64_t total = 0;
     if (n > 0) {
         if (nw == 0) return set_err(ctx, HM_E_STATE, "tiles without windows");
-        hipLaunchKernelGGL(k_tile_doc_sizes, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, P, (const uint64_t *)ctx->o_cell.p,
+        hipLaunchKernelGGL(k_tile_doc_sizes, dim3(read_grid(ctx->read_grid, n, 256)), dim3(256), 0, ctx->stream, P, (const uint64_t *)ctx->o_cell.p,
                            (const int64_t *)ctx->o_ws.p, (const int64_t *)ctx->o_cnt.p, n, (unsigned *)ctx->td_sizes.p);
         const int64_t nb = (n + SC_PER - 1) / SC_PER;
         if ((rc = ensure(ctx, ctx->td_btot, nb * 4)) || (rc = ensure(ctx, ctx->td_boff, nb * 8))) return rc;
@@ -146,7 +146,7 @@ int hm_encode_tile_updates(hm_ctx *ctx, const hm_tile_doc_cfg *cfg, int32_t out_
                            (unsigned *)ctx->td_btot.p);
         hipLaunchKernelGGL(k_cp_scan, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned *)ctx->td_btot.p, nb,
                            (unsigned long long *)ctx->td_boff.p, off + n);
-        hipLaunchKernelGGL(k_scan_add, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, off, n, (const unsigned long long *)ctx->td_boff.p);
+        hipLaunchKernelGGL(k_scan_add, dim3(read_grid(ctx->read_grid, n, 256)), dim3(256), 0, ctx->stream, off, n, (const unsigned long long *)ctx->td_boff.p);
         HIPCHK(ctx, hipGetLastError());
         HIPCHK(ctx, hipMemcpyAsync(&total, off + n, 8, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(ctx, ctx_sync(ctx, __LINE__));
@@ -160,7 +160,7 @@ int hm_encode_tile_updates(hm_ctx *ctx, const hm_tile_doc_cfg *cfg, int32_t out_
         Ph.off_end_s = cfg->end_offset_s;
         const int max_doc = tile_statement(nullptr, Ph, ~0ull, W[0], INT64_MAX, 0.0, 1, 0.0, 0.0);
         if (max_doc > TD_MAX_DOC) {   // a long CITY: no LDS staging
-            hipLaunchKernelGGL(k_tile_docs_direct, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, P, (const uint64_t *)ctx->o_cell.p,
+            hipLaunchKernelGGL(k_tile_docs_direct, dim3(read_grid(ctx->read_grid, n, 256)), dim3(256), 0, ctx->stream, P, (const uint64_t *)ctx->o_cell.p,
                                (const int64_t *)ctx->o_ws.p, (const int64_t *)ctx->o_cnt.p, (const double *)ctx->o_sp.p,
                                (const uint8_t *)ctx->o_spn.p, (const double *)ctx->o_lon.p, (const double *)ctx->o_lat.p, n,
                                (const unsigned long long *)off, (uint8_t *)ctx->td_bytes.p);
@@ -168,7 +168,7 @@ int hm_encode_tile_updates(hm_ctx *ctx, const hm_tile_doc_cfg *cfg, int32_t out_
             const size_t lds = (size_t)TD_THREADS * ((max_doc + 15) & ~15) + 32;
             if (lds > 65536)
                 HIPCHK(ctx, hipFuncSetAttribute((const void *)k_tile_docs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_tile_docs, dim3(grid_for(n, TD_THREADS)), dim3(TD_THREADS), lds, ctx->stream, P, (const uint64_t *)ctx->o_cell.p,
+            hipLaunchKernelGGL(k_tile_docs, dim3(read_grid(ctx->read_grid, n, TD_THREADS)), dim3(TD_THREADS), lds, ctx->stream, P, (const uint64_t *)ctx->o_cell.p,
                                (const int64_t *)ctx->o_ws.p, (const int64_t *)ctx->o_cnt.p, (const double *)ctx->o_sp.p,
                                (const uint8_t *)ctx->o_spn.p, (const double *)ctx->o_lon.p, (const double *)ctx->o_lat.p, n,
                                (const unsigned long long *)off, (uint8_t *)ctx->td_bytes.p);
@@ -240,7 +240,7 @@ int hm_encode_position_updates(hm_ctx *ctx, const hm_position_doc_cfg *cfg, int3
     if (n > 0) {
         const int64_t *rows = (const int64_t *)ctx->rows.p;
         HIPCHK(ctx, hipMemsetAsync(ctx->d_scratch + POSBAD_WORD, 0, 8, ctx->stream));
-        hipLaunchKernelGGL(k_pos_doc_sizes, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, P, rows, n, ctx->last_vk,
+        hipLaunchKernelGGL(k_pos_doc_sizes, dim3(read_grid(ctx->read_grid, n, 256)), dim3(256), 0, ctx->stream, P, rows, n, ctx->last_vk,
                            ctx->last_ts, (unsigned *)ctx->td_sizes.p, ctx->d_scratch + POSBAD_WORD);
         const int64_t nb = (n + SC_PER - 1) / SC_PER;
         if ((rc = ensure(ctx, ctx->td_btot, nb * 4)) || (rc = ensure(ctx, ctx->td_boff, nb * 8))) return rc;
@@ -248,7 +248,7 @@ int hm_encode_position_updates(hm_ctx *ctx, const hm_position_doc_cfg *cfg, int3
                            (unsigned *)ctx->td_btot.p);
         hipLaunchKernelGGL(k_cp_scan, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned *)ctx->td_btot.p, nb,
                            (unsigned long long *)ctx->td_boff.p, off + n);
-        hipLaunchKernelGGL(k_scan_add, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, off, n, (const unsigned long long *)ctx->td_boff.p);
+        hipLaunchKernelGGL(k_scan_add, dim3(read_grid(ctx->read_grid, n, 256)), dim3(256), 0, ctx->stream, off, n, (const unsigned long long *)ctx->td_boff.p);
         HIPCHK(ctx, hipGetLastError());
         unsigned long long hb[2] = {0, 0};
         HIPCHK(ctx, hipMemcpyAsync(&hb[0], off + n, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -257,7 +257,7 @@ int hm_encode_position_updates(hm_ctx *ctx, const hm_position_doc_cfg *cfg, int3
         if (hb[1]) return set_err(ctx, HM_E_INVALID, "%llu latest rows outside the provider/vehicle dictionaries or time buckets", hb[1]);
         total = (int64_t)hb[0];
         if ((rc = ensure(ctx, ctx->td_bytes, total + 16))) return rc;
-        hipLaunchKernelGGL(k_pos_docs, dim3(grid_for(n, 256)), dim3(256), 0, ctx->stream, P, rows, n, ctx->last_vk, ctx->last_ts,
+        hipLaunchKernelGGL(k_pos_docs, dim3(read_grid(ctx->read_grid, n, 256)), dim3(256), 0, ctx->stream, P, rows, n, ctx->last_vk, ctx->last_ts,
                            ctx->last_lat, ctx->last_lon, (const unsigned long long *)off, (uint8_t *)ctx->td_bytes.p);
         HIPCHK(ctx, hipGetLastError());
     } else {

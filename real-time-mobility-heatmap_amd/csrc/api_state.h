@@ -25,7 +25,7 @@ static int state_dump(hm_ctx *ctx, hm_state_rec *recs, int64_t n, unsigned only_
     HIPCHK(ctx, hipMemsetAsync(ctx->d_scratch + REGROW_WORD, 0, 8, ctx->stream));
     for (const auto &g : ctx->gens) {
         const GenDesc d = gen_desc(g);
-        hipLaunchKernelGGL(k_dump_gen, dim3(grid_for(int64_t(1) << g.log2cap, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, d,
+        hipLaunchKernelGGL(k_dump_gen, dim3(read_grid(ctx->read_grid, int64_t(1) << g.log2cap, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, d,
                            (GrowRec *)ctx->parts_regrow.p, ctx->d_scratch + REGROW_WORD, only_seq, true);
     }
     HIPCHK(ctx, hipGetLastError());
@@ -73,7 +73,7 @@ int hm_state_export_touched(hm_ctx *ctx, hm_state_info *info, hm_state_rec *recs
         HIPCHK(ctx, hipMemsetAsync(ctx->d_scratch + REGROW_WORD, 0, 8, ctx->stream));
         for (const auto &g : ctx->gens) {
             const GenDesc d = gen_desc(g);
-            hipLaunchKernelGGL(k_dump_gen, dim3(grid_for(int64_t(1) << g.log2cap, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, d,
+            hipLaunchKernelGGL(k_dump_gen, dim3(read_grid(ctx->read_grid, int64_t(1) << g.log2cap, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, d,
                                (GrowRec *)ctx->parts_regrow.p, ctx->d_scratch + REGROW_WORD, seq32(ctx), true);
         }
         HIPCHK(ctx, hipGetLastError());

@@ -22,6 +22,32 @@ static hipError_t udf_buf(DevBuf &b, size_t bytes) {
     if (e == hipSuccess) b.bytes = want;
     return e;
 }
+// MOBHEAT_TEST_READ_GRID for the entry points without a context (hm_cells_in_view, hm_points_in_zones): read by every
+// call, as there is no hm_create to read it in; the counts are the process's (hm_test_read_grid_info without a context)
+static ReadGrid g_udf_read_grid;
+static ReadGrid &udf_read_grid() {   // (g_udf_mu held)
+    // a getenv per call, on purpose: a test sets and unsets the variable between calls of one process, and the lookup is
+    // nothing beside the call's copies and its stream synchronisation
+    const char *m = getenv("MOBHEAT_TEST_READ_GRID");
+    g_udf_read_grid.g = m ? std::max(0, atoi(m)) : 0;
+    return g_udf_read_grid;
+}
+// what read_grid lowered: on a context since hm_create (every read-side and sink file's launches), or -- ctx NULL -- in
+// the context-free calls above, which is why it lives here
+int hm_test_read_grid_info(const hm_ctx *ctx, int64_t *launches_lowered, int64_t *least_iterations, int64_t *most_iterations) {
+    if (!launches_lowered || !least_iterations || !most_iterations) return HM_E_INVALID;
+    ReadGrid rg;
+    if (ctx) {
+        rg = ctx->read_grid;
+    } else {
+        std::lock_guard<std::mutex> lock(g_udf_mu);
+        rg = g_udf_read_grid;
+    }
+    *launches_lowered = rg.lowered;
+    *least_iterations = rg.least;
+    *most_iterations = rg.most;
+    return HM_OK;
+}
 static int udf_begin(int32_t device, UdfState *&S) {   // (g_udf_mu held)
     int ndev = 0;
     if (device < 0 || device >= 64 || hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) return HM_E_HIP;

@@ -37,7 +37,7 @@ int hm_cells_in_view(const uint64_t *cells, int64_t n, int32_t memory, int32_t d
         dkeep = (uint8_t *)S->out2.p;
     }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_cells_in_view, dim3(grid_for(n, 256, 256 * 32)), dim3(256), 0, S->stream, dcells, n, poles, *view, dkeep);
+        hipLaunchKernelGGL(k_cells_in_view, dim3(read_grid(udf_read_grid(), n, 256, 256 * 32)), dim3(256), 0, S->stream, dcells, n, poles, *view, dkeep);
         e = hipGetLastError();
     }
     if (e == hipSuccess && memory == HM_MEM_HOST) e = hipMemcpyAsync(keep_u8, dkeep, n, hipMemcpyDeviceToHost, S->stream);
@@ -83,7 +83,7 @@ int hm_window_geojson_view(hm_ctx *ctx, int64_t window_start_us, int32_t res, co
         unsigned long long *w = (unsigned long long *)G.words.p + GJW_OUT;
         HIPCHK(ctx, hipMemsetAsync(w, 0, 8, ctx->stream));
         HIPCHK(ctx, hipEventRecord(G.vev[0], ctx->stream));
-        hipLaunchKernelGGL(k_view_tiles, dim3(grid_for(m, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, (const GrowRec *)ctx->ru_out.p, m,
+        hipLaunchKernelGGL(k_view_tiles, dim3(read_grid(ctx->read_grid, m, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, (const GrowRec *)ctx->ru_out.p, m,
                            poles.north[res], poles.south[res], *view, (GrowRec *)G.vrecs.p, w);
         HIPCHK(ctx, hipEventRecord(G.vev[1], ctx->stream));
         HIPCHK(ctx, hipGetLastError());

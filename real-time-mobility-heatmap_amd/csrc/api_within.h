@@ -134,7 +134,7 @@ int hm_points_in_zones(const hm_zones *zones, const double *lat, const double *l
         dhits = (unsigned *)S->out1.p;
     }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_points_in_zones, dim3(grid_for(n, 256 * DUMP_PER)), dim3(256), 0, S->stream,
+        hipLaunchKernelGGL(k_points_in_zones, dim3(read_grid(udf_read_grid(), n, 256 * DUMP_PER)), dim3(256), 0, S->stream,
                            zones_view(S->zones.p, zones->n_zones, ne), dlat, dlon, n, dfirst, dhits);
         e = hipGetLastError();
     }
@@ -245,7 +245,7 @@ static int within_positions(hm_ctx *ctx, const hm_zones *zones, int n_edges, int
         (rc = within_begin(ctx, zones, n_edges, zs)))
         return rc;
     HIPCHK(ctx, hipEventRecord(W.ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_pos_within, dim3(grid_for(cap, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, (const PosSlot *)P.tab, cap, zs,
+    hipLaunchKernelGGL(k_pos_within, dim3(read_grid(ctx->read_grid, cap, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, (const PosSlot *)P.tab, cap, zs,
                        (long long)since_us, emit ? (hm_position_rec *)W.out.p : nullptr, (int *)W.zone.p, keys,
                        (unsigned long long *)W.tot.p, (unsigned long long *)W.words.p);
     HIPCHK(ctx, hipEventRecord(W.ev[1], ctx->stream));
@@ -269,7 +269,7 @@ static int within_window(hm_ctx *ctx, int64_t window_start_us, int32_t res, cons
         (rc = within_begin(ctx, zones, n_edges, zs)))
         return rc;
     HIPCHK(ctx, hipEventRecord(W.ev[0], ctx->stream));
-    hipLaunchKernelGGL(k_within_tiles, dim3(grid_for(g, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, (const GrowRec *)ctx->ru_out.p, g, zs,
+    hipLaunchKernelGGL(k_within_tiles, dim3(read_grid(ctx->read_grid, g, 256 * DUMP_PER)), dim3(256), 0, ctx->stream, (const GrowRec *)ctx->ru_out.p, g, zs,
                        emit ? (GrowRec *)W.out.p : nullptr, (int *)W.zone.p, (unsigned long long *)W.tot.p, (unsigned long long *)W.words.p);
     HIPCHK(ctx, hipEventRecord(W.ev[1], ctx->stream));
     if ((rc = within_scan_done(ctx, zs, g, emit, n))) return rc;

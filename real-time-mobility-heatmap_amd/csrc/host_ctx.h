@@ -18,6 +18,14 @@ struct Inputs {   // a batch's device columns
     int64_t n;
 };
 
+// MOBHEAT_TEST_READ_GRID (tests): the largest grid of the read side's and the sink's streaming kernels, and what
+// lowering did -- the launches it lowered and the fewest / most grid-stride iterations of a workgroup in any of them
+// (read_grid, hm_test_read_grid_info)
+struct ReadGrid {
+    int g = 0;   // 0: unset
+    int64_t lowered = 0, least = 0, most = 0;
+};
+
 struct hm_ctx {
     hm_config cfg;
     int device = 0;
@@ -134,6 +142,7 @@ struct hm_ctx {
     int64_t table_regimes[6] = {0, 0, 0, 0, 0, 0};
     int test_agg_grid = 0;          // MOBHEAT_TEST_AGG_GRID: k_agg's spans as if the device had this many CUs (tests; 0: unset)
     unsigned test_agg_cap = 0;      // MOBHEAT_TEST_AGG_CAP: the floor of agg_cap instead of 4096 (tests; 0: unset)
+    ReadGrid read_grid;             // MOBHEAT_TEST_READ_GRID (tests; g = 0: unset)
     // hm_decode_json (row f1): the values on the device, the decoded columns, the string dictionaries
     struct Dict {
         DevBuf tab, slot_of, occ, slots, code_of_slot, clen, coff, cbytes, btot, boff;
@@ -549,6 +558,18 @@ static int grid_for(int64_t n, int threads, int max_blocks = 256 * 16) {
     if (b < 1) b = 1;
     if (b > max_blocks) b = max_blocks;
     return (int)b;
+}
+// grid_for for the read side's and the sink's streaming kernels: at most rg.g workgroups under MOBHEAT_TEST_READ_GRID, so
+// that a few thousand items are several grid-stride iterations of every workgroup; unset, grid_for unchanged.  A grid it
+// lowers is counted, with the iterations of its busiest workgroup.
+static int read_grid(ReadGrid &rg, int64_t n, int threads, int max_blocks = 256 * 16) {
+    const int full = grid_for(n, threads, max_blocks);
+    if (rg.g <= 0 || full <= rg.g) return full;
+    const int64_t per = (int64_t)threads * rg.g, it = (n + per - 1) / per;
+    rg.least = rg.lowered ? std::min(rg.least, it) : it;
+    rg.most = std::max(rg.most, it);
+    rg.lowered++;
+    return rg.g;
 }
 
 static uint64_t next_pow2(uint64_t v) {

@@ -239,6 +239,7 @@ SIGNATURES = {
     "hm_selftest_positions_within": (c_i32, [_P(HmZones), c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, _P(c_i64)]),
     "hm_selftest_tiles_within": (c_i32, [_P(HmZones), c_vp, c_i64, c_vp, c_vp, c_vp, _P(c_i64)]),
     "hm_within_info": (c_i32, [c_vp, c_vp, c_i32]),
+    "hm_test_read_grid_info": (c_i32, [c_vp, c_vp, c_vp, c_vp]),
     "hm_selftest_float_repr_host": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "hm_selftest_float_repr_device": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32]),
     "hm_abi_version": (c_i32, []),
@@ -280,6 +281,14 @@ def check(rc, ctx=None, what="mobheat"):
         msg = lib.hm_last_error(ctx)
         raise MobheatError(f"{what} failed ({rc}): {msg.decode() if msg else ''}", rc)
     return rc
+
+
+def read_grid_info(ctx=None):
+    """{"launches_lowered", "least_iterations", "most_iterations"} of MOBHEAT_TEST_READ_GRID on a context, or -- ctx None --
+    of the process's context-free calls (hm_cells_in_view, hm_points_in_zones)."""
+    v = [ctypes.c_int64() for _ in range(3)]
+    check(load().hm_test_read_grid_info(ctx, *(ctypes.byref(x) for x in v)), ctx, "hm_test_read_grid_info")
+    return {"launches_lowered": v[0].value, "least_iterations": v[1].value, "most_iterations": v[2].value}
 
 
 def ptr(a):

@@ -907,6 +907,10 @@ class HeatmapEngine:
         check(self._lib.hm_within_info(self._ctx, v, 6), self._ctx, "hm_within_info")
         return {"scanned": v[0], "kept_since": v[1], "in_zone": v[2], "zones": v[3], "vertices": v[4], "scan_us": v[5]}
 
+    def read_grid_info(self):
+        """What MOBHEAT_TEST_READ_GRID did on this engine since it was created (hm_test_read_grid_info)."""
+        return _lib.read_grid_info(self._ctx)
+
     def encode_tile_updates_device(self, city, ttl_minutes):
         """The same, left on the device: (device pointer of the bytes, of the offsets, n statements)."""
         n = ctypes.c_int64()

@@ -187,3 +187,43 @@ def test_query_selftests_against_numpy(name):
     assert not tot["newest_us"].any() and (out.size > 0 or name == "degenerate")
     if name == "overlapping_squares":   # a point counts in every zone that contains it
         assert tot["n"].sum() > out.size
+
+
+@pytest.mark.parametrize("name", wc.STAGED)
+def test_staged_sets_host_execution(name):
+    """the sets at the LDS staging's and the LDS totals' edges: their geometry is what their names say, the host execution
+    equals numpy on random points, vertices and on-edge points, and the exact rule wherever it decides"""
+    from mobheat import _lib, readside
+    zones = wc.zone_set(name)
+    edges = np.diff(zones.ring_verts)[np.asarray(zones.zone_rings[:-1])]   # (one ring per zone)
+    assert zones.n_zones == zones.ring_verts.size - 1
+    if name == "stage_span":
+        assert edges.tolist() == [3, 1500, 3] and 3 % wc.STAGE and 1503 % wc.STAGE and 1503 > 2 * wc.STAGE
+    if name == "stage_end":
+        assert edges.tolist() == [509, 3, 512] and 509 + 3 == wc.STAGE
+    if name.startswith("triangles"):
+        assert zones.n_zones == {"triangles1024": wc.ZLDS, "triangles1025": wc.ZLDS + 1}[name] and np.all(edges == 3)
+    la, lo = wc.random_points(3000, seed=17)
+    ela, elo = wc.edge_points(zones, stride=3)
+    lat, lon = np.r_[la, zones.lat[::5], ela], np.r_[lo, zones.lon[::5], elo]
+    first, hits = _lib.points_in_zones_selftest(zones, lat, lon)
+    nfirst, nhits = readside.points_in_zones(zones, lat, lon)
+    assert np.array_equal(first, nfirst) and np.array_equal(hits, nhits), f"{name}: {int((hits != nhits).sum())} differ"
+    assert hits.any() and np.all((first >= 0) == (hits > 0)) and np.all(first < zones.n_zones)
+    if name in ("stage_span", "stage_end"):   # every zone of the set holds some point, the ones behind a stage end too
+        assert (readside.zone_totals_of(zones, la, lo, ts_us=np.zeros(la.size, np.int64))[1]["n"] > 0).all()
+    xla, xlo = wc.random_points(60 if name.startswith("triangles") else 150, seed=23)
+    efirst, ehits, decided = wc.exact(zones, xla, xlo)
+    xfirst, xhits = _lib.points_in_zones_selftest(zones, xla, xlo)
+    assert decided.mean() > 0.9
+    assert np.array_equal(xfirst[decided], efirst[decided]) and np.array_equal(xhits[decided], ehits[decided])
+    recs = dc.boston(2000, seed=19)
+    out, zone, tot = _lib.positions_within_selftest(zones, recs)
+    wout, wzone, wtot = wc.positions_expected(zones, recs)
+    assert out.tobytes() == wout.tobytes() and np.array_equal(zone, wzone), name
+    wc.same_totals(tot, wtot, name)
+    tiles = _tiles(2000)
+    out, zone, tot = _lib.tiles_within_selftest(zones, tiles)
+    wout, wzone, wtot = wc.tiles_expected(zones, tiles)
+    assert out.tobytes() == wout.tobytes() and np.array_equal(zone, wzone), name
+    wc.same_totals(tot, wtot, name)

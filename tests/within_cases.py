@@ -127,6 +127,58 @@ def triangles4096(side=64):
     return _zones(rings)
 
 
+def _circle(cla, clo, r, verts):
+    t = np.arange(verts) * (2.0 * np.pi / verts)
+    return [list(zip((cla + r * np.sin(t)).tolist(), (clo + r * np.cos(t)).tolist()))]
+
+
+def _regular(cla, clo, r, verts):
+    """a regular polygon of `verts` vertices, none of its edges horizontal (every one of them is an edge of the packed set)"""
+    t = (np.arange(verts) + 0.25) * (2.0 * np.pi / verts)
+    return [list(zip((cla + r * np.sin(t)).tolist(), (clo + r * np.cos(t)).tolist()))]
+
+
+_TRI_A = [[(42.22, -71.18), (42.43, -71.05), (42.25, -70.97)]]
+_TRI_B = [[(42.40, -71.15), (42.24, -71.12), (42.30, -71.00)]]
+
+
+@functools.lru_cache(maxsize=None)
+def stage_span():
+    """a 3-vertex zone, a 1500-vertex circle, a 3-vertex zone: the circle's edges are [3, 1503) of the set's, three LDS
+    stages at unaligned offsets, and the last zone starts in the middle of a stage"""
+    return _zones([_TRI_A, _circle(42.32, -71.08, 0.09, 1500), _TRI_B])
+
+
+@functools.lru_cache(maxsize=None)
+def stage_end():
+    """zones of 509, 3 and 512 edges: the second ends exactly at the first stage's end, the third is the second stage"""
+    return _zones([_regular(42.30, -71.10, 0.07, 509), _TRI_A, _regular(42.34, -71.04, 0.08, 512)])
+
+
+def _triangles(n, side=33):
+    dla, dlo = (BOX[1] - BOX[0]) / side, (BOX[3] - BOX[2]) / side
+    rings = []
+    for k in range(n):
+        i, j = divmod(k, side)
+        a = (BOX[0] + i * dla, BOX[2] + j * dlo)
+        rings.append([[a, (a[0], a[1] + dlo), (a[0] + dla, a[1] + 0.5 * dlo)]])
+    return _zones(rings)
+
+
+@functools.lru_cache(maxsize=None)
+def triangles1024():
+    """exactly ZLDS one-triangle zones: the last set whose totals a workgroup keeps in LDS"""
+    return _triangles(ZLDS)
+
+
+@functools.lru_cache(maxsize=None)
+def triangles1025():
+    """ZLDS + 1 one-triangle zones: the first set whose totals go straight to memory"""
+    return _triangles(ZLDS + 1)
+
+
+# the sets at the LDS staging's and the LDS totals' edges (tests/test_gpu_read_grid.py runs them over several grid iterations)
+STAGED = ("stage_span", "stage_end", "triangles1024", "triangles1025")
 SMALL = ("triangle", "square_with_hole", "concave_c", "overlapping_squares", "mesh", "horizontal_edge", "degenerate")
 LARGE = ("circles", "triangles4096")
 ALL = SMALL + LARGE
