@@ -919,7 +919,10 @@ int hm_selftest_float_repr_device(const double *x, int64_t n, uint8_t *text, int
  * [17] emissions of a full reducing table before a bucket's last one, summed over buckets, [18] the bucket capacity
  * (records per sub-bucket) the batch ran with.  Tests reach them on small batches with MOBHEAT_TEST_AGG_GRID=<g> (the
  * aggregation's row spans as if the device had g compute units) and MOBHEAT_TEST_AGG_CAP=<f> (the floor of the bucket
- * capacity instead of 4096), read at hm_create. */
+ * capacity instead of 4096), read at hm_create.  [19] the rows the per-event pass listed as candidates of the
+ * latest-position dedup (a superset of the latest rows), or -1 when the batch's dedup ran from the per-row flags
+ * instead: the list held fewer rows than that (max(n / 16, 65536); tests: MOBHEAT_TEST_CAND_CAP=<rows>, read at
+ * hm_create), or the fused per-vkey max gave up. */
 int hm_last_counts(const hm_ctx *ctx, int64_t *c, int32_t n);
 /* Version of the persistent tile state: incremented when a batch starts merging into it (hm_process_batch,
  * hm_stage_merge, growth).  A call that failed without changing it left the state as it was (-1: ctx NULL). */

@@ -137,6 +137,9 @@ int hm_create(const hm_config *cfg, hm_ctx **out) {
     // pipelines every binned batch in K chunks (tests, A/B), "auto": batches of >= PIPE_MIN_ROWS rows in PIPE_CHUNKS chunks
     if (const char *m = getenv("MOBHEAT_PIPELINE")) ctx->pipe_mode = !strcmp(m, "auto") ? -1 : std::max(0, std::min(atoi(m), hm_ctx::PIPE_MAX));
     if (const char *m = getenv("MOBHEAT_TEST_SLAB_CAP")) ctx->test_slab_cap = (unsigned)std::max(0, atoi(m));
+    // MOBHEAT_TEST_CAND_CAP (tests): the dedup's candidate list holds that many rows, so that a small batch overflows it
+    // and its dedup reruns from the flags
+    if (const char *m = getenv("MOBHEAT_TEST_CAND_CAP")) ctx->test_cand_cap = std::max(0, atoi(m));
     // MOBHEAT_TEST_MERGE_TAGS (tests): at most that many bytes of resident region tags per merge workgroup -- 0: no
     // region is resident, every record probes through HBM; less than the batch's windows need: the merge with the
     // HBM-probing fallback, the windows that still fit resident; MOBHEAT_TEST_MERGE_COOP=0|1 (tests): the per-lane or the
@@ -192,7 +195,7 @@ int hm_create(const hm_config *cfg, hm_ctx **out) {
         const size_t tp = sizeof(TilePartial);
         (void)tp;
         if (ensure(ctx, ctx->flags, n) || ensure(ctx, ctx->win, n) || ensure(ctx, ctx->rows, n * 8) ||
-            ensure(ctx, ctx->keys, n * 8) || ensure(ctx, ctx->slow, n * 4) ||
+            ensure(ctx, ctx->keys, n * 8) || ensure(ctx, ctx->slow, n * 4) || ensure_cand_buffers(ctx, n) ||
             ensure(ctx, ctx->parts_sorted, n * sizeof(EventRec)) ||
             ensure(ctx, ctx->s_cell, n * 8) || ensure(ctx, ctx->s_ws, n * 8) || ensure(ctx, ctx->s_cnt, n * 8) ||
             ensure(ctx, ctx->s_sp, n * 8) || ensure(ctx, ctx->s_spn, n) || ensure(ctx, ctx->s_lon, n * 8) ||
@@ -233,6 +236,7 @@ void hm_destroy(hm_ctx *ctx) {
     if (ctx->merge_stream) (void)hipStreamSynchronize(ctx->merge_stream);
     DevBuf *bufs[] = {&ctx->pl_cur, &ctx->pl_slow, &ctx->pl_O, &ctx->pl_cnt, &ctx->pl_T, &ctx->in_lat, &ctx->in_lon, &ctx->in_ts, &ctx->in_speed, &ctx->in_sv, &ctx->in_vkey, &ctx->in_rv,
                       &ctx->cell, &ctx->wstart, &ctx->flags, &ctx->win, &ctx->rows, &ctx->block_counts, &ctx->block_offs,
+                      &ctx->cand_rows, &ctx->cand_bm,
                       &ctx->partials, &ctx->cands, &ctx->slow, &ctx->parts_sorted, &ctx->parts_regrow, &ctx->parts_regrow_sorted, &ctx->stage_meta, &ctx->stage_C, &ctx->stage_P,
                       &ctx->stage_SO, &ctx->stage_SP, &ctx->stage_T, &ctx->cands_recv, &ctx->stage_tmp, &ctx->rp_H, &ctx->rp_O,
                       &ctx->rp_btot, &ctx->rp_boff,
@@ -329,6 +333,7 @@ int hm_last_counts(const hm_ctx *ctx, int64_t *c, int32_t n) {
     if (n > 11) c[11] = ctx->last_ring_direct;
     if (n > 12) c[12] = ctx->last_merge_variant;
     for (int i = 13; i < n && i < 19; i++) c[i] = ctx->last_counts[3] ? ctx->table_regimes[i - 13] : 0;
+    if (n > 19) c[19] = ctx->last_cand_count;
     return HM_OK;
 }
 
@@ -379,11 +384,16 @@ int hm_process_batch(hm_ctx *ctx, int64_t epoch_id, const hm_batch_in *in, int32
     ctx->last_table = table;
     // 4. dedup over the batch's valid rows -- on the side stream, concurrently with step 3 (the rerun of the max on a
     // full table, after the fused one gave up, prepares that table on the main stream: it stays there)
-    ctx->dedup_side = s1.dedup_retry == 0 && !ctx->dedup_main;
+    // (the side stream's dedup runs from k_ingest's candidate list: a batch with more candidates than the list holds is
+    // rerun from its flags, like one whose fused max gave up but on the fused table)
+    const bool cand_over = cand_overflowed(ctx, s1);
+    ctx->dedup_side = s1.dedup_retry == 0 && !cand_over && !ctx->dedup_main;
+    ctx->last_cand_count = ctx->dedup_side ? (int64_t)s1.n_cands : -1;
     // (launched behind k_ingest -- phase_local, early_dedup -- or else here, ahead of the partition: 1-3% faster on the
     // bench than launched after the merge path's kernels, ~5% faster than overlapping the merge only, 2-4% faster than
     // behind k_ev_hist -- profiles/r3/r3ab12/, r3ab13/)
-    if (ctx->dedup_early && !ctx->dedup_side)   // (the fused max gave up: the rerun below overwrites its outputs)
+    if (ctx->dedup_early && !ctx->dedup_side)   // (the fused max gave up, or the list overflowed: the rerun below
+                                                // overwrites its outputs)
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_ev[2], 0));
     if (ctx->dedup_side && !ctx->dedup_early) {
         HIPCHK(ctx, hipEventRecord(ctx->side_ev[0], ctx->stream));
@@ -401,7 +411,7 @@ int hm_process_batch(hm_ctx *ctx, int64_t epoch_id, const hm_batch_in *in, int32
         if ((rc = merge_events(ctx, I, n_agg))) return rc;
     }
     if (!ctx->dedup_side) {
-        if ((rc = phase_dedup(ctx, &I, nullptr, I.n, true))) return rc;
+        if ((rc = phase_dedup(ctx, &I, nullptr, I.n, !(cand_over && s1.dedup_retry == 0 && !ctx->dedup_main)))) return rc;
     } else {
         HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_ev[2], 0));
     }
@@ -417,6 +427,8 @@ int hm_process_batch(hm_ctx *ctx, int64_t epoch_id, const hm_batch_in *in, int32
     if (s2.merge_hbm) ctx->last_merge_variant |= 8;
     if (s2.overflow) return set_err(ctx, HM_E_OVERFLOW, "device hash table overflow");
     if (s2.bad_vkey) return set_err(ctx, HM_E_INVALID, "vkey UINT64_MAX is reserved (%llu rows)", s2.bad_vkey);
+    if (ctx->dedup_side && I.n > 0 && ctx->h_scratch[CANDOVER_WORD])
+        return set_err(ctx, HM_E_STATE, "the dedup's candidate list overflowed unseen (%llu candidates)", s1.n_cands);
     int64_t n_rows = (int64_t)ctx->h_scratch[255];
     ctx->last_n_latest = n_rows;
     ctx->last_vk = I.vk;

@@ -154,8 +154,14 @@ int hm_stage_send(hm_ctx *ctx, const int64_t *summaries, void *send_buf, int64_t
     ctx->census_ready = false;   // (the owner counts what it receives)
     // local dedup over rows -> local winners -> candidates, counted per owner (launched in hm_stage_ingest unless the
     // fused max gave up: then rerun here after it)
+    // (the early one runs from k_ingest's candidate list, and so does the one launched here when nothing asks for the
+    // flags: a list that overflowed is rerun from the flags like a give-up, on the fused table)
     if (ctx->dedup_early) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_ev[2], 0));
-    if ((!ctx->dedup_early || s1.dedup_retry != 0) && (rc = phase_dedup(ctx, &I, nullptr, I.n, s1.dedup_retry != 0))) return rc;
+    const bool from_flags = s1.dedup_retry != 0 || cand_overflowed(ctx, s1) || ctx->dedup_main;
+    ctx->last_cand_count = from_flags ? -1 : (int64_t)s1.n_cands;
+    if (from_flags) rc = phase_dedup(ctx, &I, nullptr, I.n, s1.dedup_retry != 0);
+    else rc = ctx->dedup_early ? HM_OK : phase_dedup_list(ctx, &I, ctx->stream);
+    if (rc) return rc;
     if ((rc = ensure(ctx, ctx->cands, std::max<int64_t>(I.n, 1) * sizeof(Cand)))) return rc;
     hipLaunchKernelGGL(k_make_cands, dim3(grid_for(std::max<int64_t>(I.n, 1), 256)), dim3(256), 0, ctx->stream,
                        (const int64_t *)ctx->rows.p, ctx->d_scratch + 255, I.vk, I.ts, ctx->rank, (Cand *)ctx->cands.p);

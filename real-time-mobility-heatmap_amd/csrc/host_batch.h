@@ -38,6 +38,20 @@ static unsigned slab_cap_for(int64_t n, double skew, int64_t nbins) {
 // critical path (profiles/r5/r5tl/)
 static int launch_side_dedup(hm_ctx *ctx, const Inputs *I);
 static int bin_offsets(hm_ctx *ctx);
+// the dedup's candidate list and winners' bitmap for a batch of n rows (the bitmap in whole 16-B quads, zeroed when it
+// is allocated: the compaction returns it to zero)
+static int64_t cand_cap_for(const hm_ctx *ctx, int64_t n) {
+    return ctx->test_cand_cap > 0 ? ctx->test_cand_cap : std::max<int64_t>(n / 16, 65536);
+}
+static int64_t bitmap_words(int64_t n) { return (std::max<int64_t>(n, 1) + 127) / 128 * 4; }
+static int ensure_cand_buffers(hm_ctx *ctx, int64_t n) {
+    int rc;
+    if ((rc = ensure(ctx, ctx->cand_rows, (size_t)cand_cap_for(ctx, n) * sizeof(unsigned int)))) return rc;
+    const size_t had = ctx->cand_bm.bytes;
+    if ((rc = ensure(ctx, ctx->cand_bm, (size_t)bitmap_words(n) * 4))) return rc;
+    if (ctx->cand_bm.bytes != had) HIPCHK(ctx, hipMemsetAsync(ctx->cand_bm.p, 0, ctx->cand_bm.bytes, ctx->stream));
+    return HM_OK;
+}
 // the batch's per-row buffers, dedup tables, bins and counters ready, k_batch_reset launched (phase_local, the
 // pipelined batch)
 static int prepare_local(hm_ctx *ctx, int64_t n, int64_t late_wm_ms, bool bin, bool sub) {
@@ -47,8 +61,10 @@ static int prepare_local(hm_ctx *ctx, int64_t n, int64_t late_wm_ms, bool bin, b
     if (ctx->dedup_early) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->side_ev[2], 0));
     ctx->dedup_early = false;
     if ((rc = ensure(ctx, ctx->flags, n)) || (rc = ensure(ctx, ctx->win, n)) || (rc = ensure(ctx, ctx->rows, n * 8)) ||
-        (rc = ensure(ctx, ctx->keys, n * 8)) || (rc = ensure(ctx, ctx->slow, n * sizeof(unsigned int))))
+        (rc = ensure(ctx, ctx->keys, n * 8)) || (rc = ensure(ctx, ctx->slow, n * sizeof(unsigned int))) ||
+        (rc = ensure_cand_buffers(ctx, n)))
         return rc;
+    ctx->cand_cap = cand_cap_for(ctx, n);
     if ((rc = dedup_prepare(ctx, ctx->dfused, dedup_fused_keys(ctx, n), true))) return rc;
     // the dense dedup table: room for the last batch's vkeys (first batch: 2^20), 2^16 .. 2^22 words; none when the
     // last batch's vkeys were not dense codes (above 2^24)
@@ -100,7 +116,7 @@ static void launch_ingest(hm_ctx *ctx, const Inputs &I, int64_t a, int64_t b, bo
                        ctx->d_scratch + GIVEUP_WORD, ctx->d_wreg, ctx->d_wcount, ctx->d_st, I.sp, I.sv,
                        (unsigned *)ctx->bin_cur.p, bin ? (EventRec *)ctx->parts_sorted.p : nullptr, ctx->slab_cap,
                        (unsigned long long *)ctx->dense.p, ctx->dense_cap, ctx->sub_bits, hs_stride(I.n) - 1, ctx->ring_polls,
-                       ctx->ring_cap);
+                       ctx->ring_cap, (unsigned int *)ctx->cand_rows.p, &ctx->d_st->n_cands, (unsigned)ctx->cand_cap);
 }
 
 static int phase_local(hm_ctx *ctx, const Inputs &I, int64_t late_wm_ms, bool allow_bin = false, bool sub = false,
@@ -184,7 +200,7 @@ static int keys_complete(hm_ctx *ctx, const Inputs &I) {
                        (unsigned int *)ctx->dfused.used.p, ctx->d_scratch + ctx->dfused.used_word, (unsigned int *)ctx->slow.p,
                        ctx->d_scratch + SLOW_WORD, ctx->d_scratch + GIVEUP_WORD, ctx->d_wreg, ctx->d_wcount, ctx->d_st, I.sp,
                        I.sv, (unsigned *)ctx->bin_cur.p, (EventRec *)nullptr, 0u, (unsigned long long *)ctx->dense.p, 0ull, 0u,
-                       (int64_t)0, 0u, 0u);
+                       (int64_t)0, 0u, 0u, (unsigned int *)nullptr, (unsigned long long *)nullptr, 0u);
     HIPCHK(ctx, hipGetLastError());
     return HM_OK;
 }
@@ -282,6 +298,45 @@ static int phase_dedup(hm_ctx *ctx, const Inputs *I, const Cand *cands, int64_t 
     }
     return HM_OK;
 }
+
+// Dedup over the batch's rows from k_ingest's candidate list (its fused max taken for usable): the winners among the
+// candidates set their bits (k_dedup_list), the bitmap is compacted in order; result as phase_dedup's.  A list that
+// overflowed leaves nothing of use here (CANDOVER_WORD set, no rows): the caller sees cand_overflowed and reruns
+// phase_dedup from the flags.
+static int phase_dedup_list(hm_ctx *ctx, const Inputs *I, hipStream_t st) {
+    int rc;
+    const int64_t n = I->n;
+    hm_ctx::DedupTable &d = ctx->dfused;
+    ctx->dlast = &d;
+    if ((rc = ensure(ctx, ctx->rows, std::max<int64_t>(n, 1) * 8))) return rc;
+    if (n == 0) {
+        HIPCHK(ctx, hipMemsetAsync(ctx->d_scratch + 255, 0, 8, st));
+        return HM_OK;
+    }
+    const int64_t nw4 = bitmap_words(n);
+    const int64_t tiles = (nw4 + BM_TILE - 1) / BM_TILE;
+    const int64_t span = (tiles + BM_MAX_GRID - 1) / BM_MAX_GRID * BM_TILE;   // words per workgroup
+    const int64_t nb = (nw4 + span - 1) / span;
+    if ((rc = ensure(ctx, ctx->block_counts, nb * sizeof(unsigned))) ||
+        (rc = ensure(ctx, ctx->block_offs, nb * sizeof(unsigned long long))))
+        return rc;
+    hipLaunchKernelGGL(k_dedup_list, dim3(grid_for(std::min(ctx->cand_cap, n), 256, 1024)), dim3(256), 0, st,
+                       (const unsigned int *)ctx->cand_rows.p, (const unsigned long long *)&ctx->d_st->n_cands,
+                       (unsigned long long)ctx->cand_cap, I->vk, I->ts, (const DedupSlot *)d.tab, d.cap - 1,
+                       (const unsigned long long *)ctx->dense.p, ctx->dense_cap, (unsigned *)ctx->cand_bm.p,
+                       ctx->d_scratch + CANDOVER_WORD);
+    hipLaunchKernelGGL(k_bm_count, dim3((unsigned)nb), dim3(BM_THREADS), 0, st, (const unsigned *)ctx->cand_bm.p, nw4, span,
+                       (unsigned *)ctx->block_counts.p);
+    hipLaunchKernelGGL(k_cp_scan, dim3(1), dim3(1024), 0, st, (const unsigned *)ctx->block_counts.p, nb,
+                       (unsigned long long *)ctx->block_offs.p, ctx->d_scratch + 255);
+    hipLaunchKernelGGL(k_bm_write, dim3((unsigned)nb), dim3(BM_THREADS), 0, st, (unsigned *)ctx->cand_bm.p, nw4, span,
+                       (const unsigned *)ctx->block_counts.p, (const unsigned long long *)ctx->block_offs.p,
+                       (int64_t *)ctx->rows.p);
+    HIPCHK(ctx, hipGetLastError());
+    return HM_OK;
+}
+// k_ingest counted more candidates than the batch's list holds (s1: the statistics read back after it)
+static bool cand_overflowed(const hm_ctx *ctx, const DevStats &s1) { return (int64_t)s1.n_cands > ctx->cand_cap; }
 
 static int ensure_outputs(hm_ctx *ctx, int64_t n_rows) {
     int rc;
@@ -396,7 +451,7 @@ static int merge_events(hm_ctx *ctx, const Inputs &I, int64_t n_rec) {
         if ((rc = windows_fit(ctx, census))) return rc;
     }
     if ((rc = merge_begin(ctx, I.n, true))) return rc;   // (only k_ingest, k_sample_heavy and the side stream's
-                                                          // k_dedup_flag ran since k_batch_reset: none counts these)
+                                                          // k_dedup_list / k_bm_* ran since k_batch_reset: none counts these)
     if (n_rec == 0) return merge_nothing(ctx);
     // binned in k_ingest: every window's table in range geometry (a row's bin is its region), and the bins' row
     // offsets are the exclusive scan of their cursors -- no partition pass over the keys and columns

@@ -58,6 +58,12 @@ struct hm_ctx {
     // per-event
     DevBuf in_lat, in_lon, in_ts, in_speed, in_sv, in_vkey, in_rv;
     DevBuf cell, wstart, flags, win, rows, block_counts, block_offs;
+    // the dedup's candidate list (k_ingest appends the rows it marks F_CAND: u32 row indices, cursor DevStats.n_cands)
+    // and the winners' bitmap (one bit per row, all zero between batches: k_bm_write clears what it reads)
+    DevBuf cand_rows, cand_bm;
+    int64_t cand_cap = 0;            // the list's room this batch: max(n / 16, 65536), or MOBHEAT_TEST_CAND_CAP
+    int64_t test_cand_cap = 0;
+    int64_t last_cand_count = -1;    // hm_last_counts [19]: the batch's candidates; -1: its dedup ran from the flags
     DevBuf partials, cands, parts_sorted, rp_H, rp_O, rp_btot, rp_boff;
     DevBuf slow;   // k_ingest's fast-path exceptions (event indices) for k_ingest_exact
     // persistent tile state: one table per live window (kernels.h: GenDesc); released tables are pooled and
@@ -461,6 +467,7 @@ constexpr int REGROW_WORD = 251; // records dumped by k_dump_gen
 constexpr int ROLLUP_WORD = 249; // 249-250: hm_window_rollup's parents emitted, parent-table overflow
 constexpr int GIVEUP_WORD = 232;
 constexpr int GAPS_WORD = 242;   // 242-243: totals of the gap / donor scans
+constexpr int CANDOVER_WORD = 231;   // k_dedup_list: the batch had more candidates than its list holds (it did nothing)
 constexpr int POSBAD_WORD = 241; // position statements: rows outside the caller's dictionaries
 constexpr int JSON_WORD = 244;   // 244-248: hm_decode_json's malformed / unsupported counts, dictionary overflow /
                                  // collisions; hm_last_latest_buckets' bucket count
@@ -805,11 +812,14 @@ static int partition(hm_ctx *ctx, const In *parts, int64_t n, int64_t &ntiles, i
 }
 
 static int phase_dedup(hm_ctx *ctx, const Inputs *I, const Cand *cands, int64_t n, bool rerun_max, hipStream_t st);
-// the batch's dedup on the side stream (hm_process_batch): side_ev[1] / [2] bracket it
+static int phase_dedup_list(hm_ctx *ctx, const Inputs *I, hipStream_t st);
+// the batch's dedup on the side stream (hm_process_batch): side_ev[1] / [2] bracket it.  It takes k_ingest's max for
+// usable (every caller's case) and so runs from the candidate list; a batch whose list overflowed is rerun from its
+// flags by the caller, after the readback of k_ingest's statistics (cand_overflowed)
 static int launch_side_dedup(hm_ctx *ctx, const Inputs *I) {
     int rc;
     HIPCHK(ctx, hipEventRecord(ctx->side_ev[1], ctx->side_stream));
-    if ((rc = phase_dedup(ctx, I, nullptr, I->n, false, ctx->side_stream))) return rc;
+    if ((rc = phase_dedup_list(ctx, I, ctx->side_stream))) return rc;
     HIPCHK(ctx, hipEventRecord(ctx->side_ev[2], ctx->side_stream));
     return HM_OK;
 }

@@ -112,7 +112,7 @@ static int pipe_overflow_rest(hm_ctx *ctx, const Inputs &I, int K, int k) {
                        (unsigned int *)ctx->dfused.used.p, ctx->d_scratch + ctx->dfused.used_word, (unsigned int *)ctx->slow.p,
                        ctx->d_scratch + SLOW_WORD, ctx->d_scratch + GIVEUP_WORD, ctx->d_wreg, ctx->d_wcount, ctx->d_st, I.sp,
                        I.sv, (unsigned *)ctx->bin_cur.p, (EventRec *)nullptr, 0u, (unsigned long long *)ctx->dense.p, 0ull, 0u,
-                       (int64_t)0, 0u, 0u);
+                       (int64_t)0, 0u, 0u, (unsigned int *)nullptr, (unsigned long long *)nullptr, 0u);
     HIPCHK(ctx, hipGetLastError());
     PIPE_STEP(ctx, "overflow: keys", k);
     ctx->keys_partial = false;

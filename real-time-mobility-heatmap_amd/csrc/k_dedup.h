@@ -243,3 +243,85 @@ __global__ __launch_bounds__(CP_THREADS) void k_cp_write(const uint8_t *__restri
     for (int q = 0; q < CP_PER; q++)
         if (v[q]) out[pos++] = b0 + q;
 }
+
+// =====================================================================================================
+// winners from k_ingest's candidate list: a bitmap of the batch's rows, compacted in order
+// =====================================================================================================
+// k_ingest appended every row it marked F_CAND to cand_rows (*n_cand of them, room for cap).  Each candidate's ts
+// against its vkey's max, looked up as k_dedup_flag does (dense word or hash slot): a winner sets its row's bit in bm
+// (one bit per row of the batch, all zero between batches).  More candidates than the list holds: nothing but
+// *over = 1 -- the host reads the same count after k_ingest and reruns the flags path.  The grid is fixed (the launch
+// precedes the host's readback of the count).
+__global__ __launch_bounds__(256) void k_dedup_list(const unsigned int *__restrict__ cand_rows,
+                                                    const unsigned long long *__restrict__ n_cand, unsigned long long cap,
+                                                    const uint64_t *__restrict__ vkey, const int64_t *__restrict__ ts,
+                                                    const DedupSlot *__restrict__ tab, unsigned long long mask,
+                                                    const unsigned long long *__restrict__ dense, unsigned long long dense_cap,
+                                                    unsigned *__restrict__ bm, unsigned long long *__restrict__ over) {
+    const unsigned long long m = *n_cand;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *over = m > cap ? 1ull : 0ull;
+    if (m > cap) return;
+    const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+    for (unsigned long long q = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; q < m; q += stride) {
+        const unsigned i = cand_rows[q];
+        const unsigned long long v = vkey[i];
+        const long long t = ts[i];
+        bool w = false;
+        if (v < dense_cap) {
+            w = (long long)(dense[v] ^ DENSE_SIGN) == t;
+        } else if (v != EMPTY_VKEY) {
+            unsigned long long h = vkey_hash(v) & mask;
+            for (unsigned long long probe = 0; probe <= mask; probe++) {
+                const DedupSlot sl = tab[h];
+                if (sl.vkey == v) { w = sl.maxts == t; break; }
+                if (sl.vkey == EMPTY_VKEY) break;
+                h = (h + 1) & mask;
+            }
+        }
+        if (w) atomicOr(&bm[i >> 5], 1u << (i & 31));
+    }
+}
+
+// Ordered compaction of the bitmap -> ascending row indices.  Workgroup b owns the words [b span, (b + 1) span) (span a
+// multiple of BM_TILE, the bitmap padded to whole 16-B quads): k_bm_count its popcount, k_cp_scan over the few hundred
+// workgroup counts, k_bm_write the rows of its set bits from its offset on, tile by tile -- and every quad it found
+// non-zero goes back to zero, so the bitmap is clean for the next batch without a pass of its own.
+constexpr int BM_THREADS = 256;
+constexpr int BM_TILE = BM_THREADS * 4;   // words per workgroup step: one 16-B load per thread
+constexpr int BM_MAX_GRID = 512;
+static_assert(BM_THREADS == CP_THREADS, "k_bm_count / k_bm_write use block_excl_scan, which sums CP_THREADS / 64 wave totals");
+__device__ __forceinline__ unsigned popc4(const uint4 &x) { return __popc(x.x) + __popc(x.y) + __popc(x.z) + __popc(x.w); }
+__global__ __launch_bounds__(BM_THREADS) void k_bm_count(const unsigned *__restrict__ bm, int64_t nw4, int64_t span,
+                                                         unsigned *__restrict__ bc) {
+    __shared__ unsigned sh[BM_THREADS / 64];
+    const int64_t w0 = (int64_t)blockIdx.x * span, w1 = w0 + span < nw4 ? w0 + span : nw4;
+    unsigned c = 0;
+    for (int64_t w = w0 + (int64_t)threadIdx.x * 4; w < w1; w += BM_TILE) c += popc4(*(const uint4 *)(bm + w));
+    unsigned total;
+    block_excl_scan(c, total, sh);
+    if (threadIdx.x == 0) bc[blockIdx.x] = total;
+}
+__global__ __launch_bounds__(BM_THREADS) void k_bm_write(unsigned *__restrict__ bm, int64_t nw4, int64_t span,
+                                                         const unsigned *__restrict__ bc, const unsigned long long *__restrict__ off,
+                                                         int64_t *__restrict__ out) {
+    __shared__ unsigned sh[BM_THREADS / 64];
+    if (bc[blockIdx.x] == 0) return;   // (the whole workgroup: no bit set in its words)
+    const int64_t w0 = (int64_t)blockIdx.x * span, w1 = w0 + span < nw4 ? w0 + span : nw4;
+    unsigned long long pos0 = off[blockIdx.x];
+    for (int64_t t0 = w0; t0 < w1; t0 += BM_TILE) {   // (every thread runs every tile: block_excl_scan's barriers)
+        const int64_t w = t0 + (int64_t)threadIdx.x * 4;
+        uint4 x = make_uint4(0u, 0u, 0u, 0u);
+        if (w < w1) x = *(const uint4 *)(bm + w);
+        const unsigned c = popc4(x);
+        unsigned total;
+        const unsigned ex = block_excl_scan(c, total, sh);
+        if (c) {
+            unsigned long long pos = pos0 + ex;
+            const unsigned q[4] = {x.x, x.y, x.z, x.w};
+            for (int k = 0; k < 4; k++)
+                for (unsigned bits = q[k]; bits; bits &= bits - 1) out[pos++] = (w + k) * 32 + (__ffs((int)bits) - 1);
+            *(uint4 *)(bm + w) = make_uint4(0u, 0u, 0u, 0u);
+        }
+        pos0 += total;
+    }
+}

@@ -8,9 +8,12 @@
 // list; a second kernel runs upstream's exact sequence (latLngToCellDeg, ~170 VGPRs) on that list only, so
 // the register footprint of the exact path never limits the occupancy of the streaming kernel.
 // =====================================================================================================
-// waves per SIMD for k_ingest: 6 (<= 80 VGPRs, no spills; 7 or 8 spill and only lengthen the waits, profiles/r3/r3ab15/,
-// profiles/r4/r4wv/); with writer waves the kernel takes 95 VGPRs, no spills: 5 waves per SIMD, the 2 workgroups of 10
-// waves a CU runs.  One function for k_ingest's attribute and the macro (tools/diag/ingest_phases.hip's kernels)
+// waves per SIMD for k_ingest: 6 (<= 80 VGPRs; 7 or 8 spill in the row loop and only lengthen the waits,
+// profiles/r3/r3ab15/, profiles/r4/r4wv/); with writer waves the kernel takes 96 VGPRs, no spills: 5 waves per SIMD, the
+// 2 workgroups of 10 waves a CU runs.  k_ingest<false> and the writer-wave kernel spill nothing; the fused binned kernel
+// (MOBHEAT_INGEST_WRITERS=0) keeps 3 loop-invariant VGPRs of cand_flush in scratch: stored once before the row loop,
+// reloaded only inside the flush (once per 64+ candidates, behind its atomic's full wait) and after the loop -- no
+// scratch access on a round's own path.  One function for k_ingest's attribute and the macro (tools/diag/ingest_phases.hip's kernels)
 constexpr int ig_waves_per_simd(int writers) { return writers ? 5 : 6; }
 #define HM_SNAP_ATTR __attribute__((amdgpu_waves_per_eu(ig_waves_per_simd(0))))
 // standalone UDF: cells only (hm_latlng_to_cell); exceptions -> slow[]
@@ -187,6 +190,21 @@ __device__ __forceinline__ unsigned ingest_writer(IngestRings<kProd> &RG, int wj
     return over;
 }
 
+// A wave's staged candidate rows buf[0, cnt) onto the batch's list: one returned atomic on the list's cursor for all of
+// them (the launches of a batch share it); a row past the list's room is counted, not stored.  The buffer is the
+// wave's own, written by its earlier instructions: LDS operations of one wave complete in order.
+constexpr int IG_CAND_STAGE = 128;   // rows staged per wave: flushed from 64 on, a round adds at most 64
+__device__ __forceinline__ void cand_flush(const unsigned int *buf, unsigned cnt, unsigned int *__restrict__ cand_rows,
+                                           unsigned long long *n_cand, unsigned cand_cap) {
+    __builtin_amdgcn_wave_barrier();
+    unsigned long long base = 0;
+    if (lane_id() == 0) base = atomicAdd(n_cand, (unsigned long long)cnt);
+    base = __shfl(base, 0, 64);
+    for (unsigned q = (unsigned)lane_id(); q < cnt; q += 64)
+        if (base + q < cand_cap) cand_rows[base + q] = buf[q];
+    __builtin_amdgcn_wave_barrier();
+}
+
 template <bool kBin, bool kKeys = false, int kWriters = 0, int kRounds = 1, int kProd = IG_THREADS / 64>
 __global__ __launch_bounds__((kProd + kWriters) * 64) __attribute__((amdgpu_waves_per_eu(ig_waves_per_simd(kWriters)))) void k_ingest(
     const double *__restrict__ lat, const double *__restrict__ lon, const int64_t *__restrict__ ts,
@@ -196,7 +214,8 @@ __global__ __launch_bounds__((kProd + kWriters) * 64) __attribute__((amdgpu_wave
     unsigned long long *n_slow, unsigned long long *dgiveup, unsigned long long *wreg, unsigned long long *wcount,
     DevStats *st, const double *__restrict__ speed, const uint8_t *__restrict__ speed_valid, unsigned *__restrict__ bin_cur,
     EventRec *__restrict__ slabs, unsigned slab_cap, unsigned long long *__restrict__ dense, unsigned long long dense_cap,
-    unsigned sub_bits, int64_t smask, unsigned ring_polls, unsigned ring_cap) {
+    unsigned sub_bits, int64_t smask, unsigned ring_polls, unsigned ring_cap, unsigned int *__restrict__ cand_rows,
+    unsigned long long *n_cand, unsigned cand_cap) {
     static_assert(!(kBin && kKeys), "k_ingest: kKeys runs unbinned");
     static_assert(kWriters == 0 ? kProd * 64 == IG_THREADS : kBin, "k_ingest: writer waves belong to the binned kernel");
     constexpr int kRows = kProd * 64, kThreads = (kProd + kWriters) * 64;   // a round's rows; the workgroup
@@ -213,6 +232,8 @@ __global__ __launch_bounds__((kProd + kWriters) * 64) __attribute__((amdgpu_wave
     __shared__ unsigned dskip;                    // the fused dedup has given up (*dgiveup) -- skip it
     __shared__ long long tmax_l[kThreads];        // per-thread max ts (an LDS max per row instead of 2 live registers)
     __shared__ long long vmax_l[kThreads];        // per-thread max vkey + 1 of the deduplicated rows (the same way)
+    __shared__ unsigned int cand_l[kKeys ? 1 : kProd][IG_CAND_STAGE];   // each producer wave's staged dedup candidates
+    unsigned n_cl = 0;                                                  // (their number: wave-uniform)
     for (int k = threadIdx.x; k < 60; k += kThreads) (&Fc[0][0])[k] = (&c_tab.faceCenterPoint[0][0])[k];
     for (int k = threadIdx.x; k < 120; k += kThreads) (&Fu[0][0][0])[k] = (&c_tab.fastU[res & 1][0][0][0])[k];
     // _faceIjkToH3's packed base-cell and digit tables in LDS (11.2 KB): from __constant__ memory they were lane-indexed vector loads
@@ -418,12 +439,31 @@ __global__ __launch_bounds__((kProd + kWriters) * 64) __attribute__((amdgpu_wave
             wave_count_slots(agg && wslot >= 0, wslot, WC.cnt);
             if (agg && wslot < 0) atomicAdd(&wcount[widx], 1ull);
         }
+        // the dedup's candidates as a list (k_dedup_list looks only at these; a row past the list's room is counted,
+        // not stored, and the batch's dedup falls back to the flags)
+        // (staged in the wave's LDS buffer and appended a wave's worth at a time: one returned atomic per round that has
+        // a candidate -- a quarter of the bench's rounds -- waited for every load in flight, the next round's prefetched
+        // columns among them, and made the ingest 0.8-1.0 ms slower, profiles/r8/r8c/)
+        if constexpr (!kKeys) {
+            const unsigned long long cm = __ballot(cand);
+            if (cm) {
+                // (the candidates below this lane, counted from the scalar mask: no 64-bit lane mask in registers)
+                const unsigned below = __builtin_amdgcn_mbcnt_hi((unsigned)(cm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)cm, 0u));
+                if (cand) cand_l[wave][n_cl + below] = (unsigned int)i;
+                n_cl += (unsigned)__popcll(cm);   // (< 64 before: at most 127 of the buffer's 128)
+                if (n_cl >= 64) {
+                    cand_flush(cand_l[wave], n_cl, cand_rows, n_cand, cand_cap);
+                    n_cl = 0;
+                }
+            }
+        }
         // poll the give-up flag now and then (its own cache line)
         if (threadIdx.x == 0 && (round & 15) == 15 && !dskip)
             __hip_atomic_store(&dskip, __hip_atomic_load(dgiveup, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0 ? 1u : 0u,
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     if constexpr (kKeys) return;   // (no census, no statistics: the batch's first pass counted them)
+    if (n_cl) cand_flush(cand_l[wave], n_cl, cand_rows, n_cand, cand_cap);   // (a writer wave staged none)
     if constexpr (kWriters > 0) {
         if (writer) binover = ingest_writer<kProd, kWriters, kRounds>(RG, wave - kProd, bin_cur, slabs, slab_cap);
         else ring_publish(&RG.r[wave].done, 1u);   // (after the wave's last tail)

@@ -192,7 +192,8 @@ struct DevStats {
     unsigned long long merge_hbm;   // k_merge_owned workgroups with a record of a window not resident in LDS, probed
                                     // through HBM (hm_last_counts [12], bit 8; growth's rehash merges are not counted)
     unsigned long long n_dedup_used;
-    unsigned long long n_cands;
+    unsigned long long n_cands;     // k_ingest: rows marked F_CAND -- the cursor of the dedup's candidate list (cand_rows),
+                                    // shared by a batch's launches; may exceed the list's room (then the flags path)
     unsigned long long overflow;    // nonzero: a hash table probe bound was exceeded
     unsigned long long bad_vkey;
     unsigned long long dedup_retry; // k_ingest: a vkey probe hit its bound; rerun k_dedup_max on a larger table

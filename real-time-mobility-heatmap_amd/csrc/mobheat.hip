@@ -33,7 +33,9 @@
 //   table mode    k_agg + k_bin_reduce aggregate in LDS first (one partial per key), then partition + merge
 //   k_fill_gaps   the per-bin row segments -> dense update-mode rows (in place)
 //   eviction      (watermark, :107) releases a window's whole table; k_dump_gen + a rehash merge grow one
-//   k_dedup_flag  latest position per (provider, vehicleId): rows whose ts equals the max (:204-207)
+//   k_dedup_list  latest position per (provider, vehicleId): rows whose ts equals the max (:204-207), looked for among
+//                 the candidates k_ingest listed; their bits compacted in order (k_bm_count / k_bm_write).  k_dedup_flag
+//                 over every row's flag when the list overflowed or the fused max gave up
 //   [multi-GPU: records grouped by owner rank, exchanged by the caller with RCCL all-to-all (api_stage.h)]
 //
 // Semantics follow SURVEY.md App. A (Spark 3.5.1): see DESIGN.md for the rules and their provenance.

@@ -939,13 +939,13 @@ class HeatmapEngine:
                 "allocs_frees": int(ms[13])}
 
     def last_counts(self):
-        c = (ctypes.c_int64 * 19)()
-        check(self._lib.hm_last_counts(self._ctx, c, 19), self._ctx)
+        c = (ctypes.c_int64 * 20)()
+        check(self._lib.hm_last_counts(self._ctx, c, 20), self._ctx)
         return {"state_new": c[0], "partials": c[1], "tiles": c[2], "table_mode": bool(c[3]), "evicted": c[4],
                 "sent": c[5], "allocs": c[6], "frees": c[7], "binned": bool(c[8]), "self_held": c[9],
                 "pipe_chunks": c[10], "ring_direct": c[11], "merge_variant": c[12], "agg_flushes": c[13],
                 "agg_spill_probe": c[14], "agg_spill_cap": c[15], "bin_spill_probe": c[16], "bin_emits": c[17],
-                "agg_cap": c[18]}
+                "agg_cap": c[18], "dedup_candidates": c[19]}
 
     def _result_from_host(self, out, copy=True):
         def arr(p, n, dt):
