@@ -884,6 +884,57 @@ int hm_selftest_tiles_within(const hm_zones *zones, const hm_state_rec *recs, in
  * events around it).  All 0 before the first call. */
 int hm_within_info(const hm_ctx *ctx, int64_t *v, int32_t n);
 
+/* ---- change between two live windows: where traffic rises or falls against the window before ----
+ * change(A, B, r): A = live window window_start_us (the current one), B = live window base_start_us (the base),
+ * 0 <= r <= h3_res.  With RA = hm_window_rollup(A, r) and RB = hm_window_rollup(B, r), the result holds one pair per cell
+ * of cells(RA) U cells(RB), in no particular order: cur is, bit for bit, RA's record of the cell and base RB's; a window
+ * without the cell (or a window that is not live) contributes the zero record {cell, that window's start, 0, 0, 0.0,
+ * 0.0, 0.0, 0}.  Nothing is added across windows; countChange = cur.count - base.count as int64 (counts are >= 0: no
+ * overflow).  Neither window live: *n = 0.  window_start_us == base_start_us: HM_E_INVALID.  A resolution out of range, a
+ * call between stage calls and a parent-table overflow are reported as hm_window_rollup reports them.
+ * view (NULL: none) keeps a pair iff hm_window_geojson_view's rule keeps its cell, before any ranking.
+ * Outputs are library-owned with buffers of their own, in device or pinned host memory per out_memory, valid until the
+ * next call on the context; the calls read the state only (hm_state_version, the tile and positions states, a checkpoint
+ * export in progress and a streamed statement encode are unaffected); a repeated call of the same size allocates
+ * nothing.  A change call counts as a roll-up for hm_window_rollup's buffers: its records handed out on the device, and
+ * the parent table hm_window_raster answers from, are valid until the next roll-up OR change call. */
+typedef struct hm_change_rec {   /* 128 B */
+    hm_state_rec cur;    /* RA's record of the cell; absent: {cell, window_start_us, 0, 0, 0.0, 0.0, 0.0, 0} */
+    hm_state_rec base;   /* RB's record of the cell; absent: {cell, base_start_us,   0, 0, 0.0, 0.0, 0.0, 0} */
+} hm_change_rec;
+#define HM_CHANGE_RISING 0    /* countChange descending */
+#define HM_CHANGE_FALLING 1   /* countChange ascending */
+#define HM_CHANGE_ABS 2       /* |countChange| descending (+c and -c tie) */
+/* every pair.  On a shard context: the rank's own cells (a caller adds the halves of equal cell across ranks). */
+int hm_window_change(hm_ctx *ctx, int64_t window_start_us, int64_t base_start_us, int32_t res, const hm_view *view /* NULL: no filter */,
+                     int32_t out_memory, const hm_change_rec **recs, int64_t *n);
+/* the first min(k, n) pairs of `order`, in that order, each whole and unchanged; ties break on the cell ascending as
+ * uint64, then on the pair's index (the top's key, hm_top_records).  k outside 0..HM_TOP_MAX or an unknown order:
+ * HM_E_INVALID, nothing touched.  A shard context: HM_E_UNSUPPORTED, as hm_window_top. */
+int hm_window_change_top(hm_ctx *ctx, int64_t window_start_us, int64_t base_start_us, int32_t res, const hm_view *view /* NULL: no filter */,
+                         int32_t order, int64_t k, int32_t out_memory, const hm_change_rec **recs, int64_t *n);
+/* the same pairs as a FeatureCollection encoded where they lie: feature i is hm_window_geojson's feature of pair i's cur
+ * half with ,"baseCount":<int>,"baseAvgSpeedKmh":<repr>,"countChange":<int> after windowEnd (baseAvgSpeedKmh by
+ * avgSpeedKmh's rule: 0.0 without a speed).  k < 0: every pair in the join's order (order is ignored); else the ranked
+ * ones (k <= HM_TOP_MAX; a shard context: HM_E_UNSUPPORTED).  Body, offsets and *n as hm_window_geojson's; nothing
+ * selected: the 42-byte empty body.  recs (optional): the pairs in feature order, pinned host memory. */
+int hm_window_geojson_change(hm_ctx *ctx, int64_t window_start_us, int64_t base_start_us, int32_t res, const hm_geojson_cfg *cfg,
+                             const hm_view *view /* NULL: no filter */, int32_t order, int64_t k, int32_t out_memory,
+                             const uint8_t **bytes, const int64_t **offsets, int64_t *n, const hm_change_rec **recs);
+/* Host execution (no GPU) from two record arrays (cells distinct within each), with the kernels' pair-building, key and
+ * comparator code: the zero halves carry window_start_us / base_start_us.  k < 0: every pair, sorted by cell; else the
+ * first min(k, n) of `order`.  out: room for n_cur + n_base pairs (or min(k, that)). */
+int hm_selftest_window_change(const hm_state_rec *cur, int64_t n_cur, const hm_state_rec *base, int64_t n_base,
+                              int64_t window_start_us, int64_t base_start_us, int32_t order, int64_t k, hm_change_rec *out,
+                              int64_t *n_out);
+/* host execution of the encoder on n pairs, as hm_selftest_tile_features */
+int hm_selftest_change_features(const hm_geojson_cfg *cfg, const hm_change_rec *pairs, int64_t n, uint8_t *bytes, int64_t cap,
+                                int64_t *offsets);
+/* up to n of, for the last change call on the context: [0] cells in RA, [1] cells in RB, [2] cells in both, [3] pairs
+ * after the view, [4] pairs returned, [5] device microseconds of the change's own kernels (HIP events around the join,
+ * the view and the ranking; the two roll-ups excluded).  All 0 before the first call. */
+int hm_change_info(const hm_ctx *ctx, int64_t *v, int32_t n);
+
 /* Tests: MOBHEAT_TEST_READ_GRID=<G>, read at hm_create (and by every hm_cells_in_view / hm_points_in_zones on a device),
  * runs the streaming kernels of the read side (view, roll-up, density, within, raster, GeoJSON, positions export), of the
  * state dump and of the sink on at most G workgroups, so that a few thousand items are several grid-stride iterations

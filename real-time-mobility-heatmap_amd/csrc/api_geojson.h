@@ -86,9 +86,10 @@ static int gj_out(hm_ctx *ctx, int64_t n, int64_t body_len, int32_t out_memory, 
 }
 
 // the features of n device records: sizes -> scan -> write -> out.  dist_m (optional, device): a distance per record
-// for the near bodies' distanceM
+// for the near bodies' distanceM.  pairs: recs are the change's n pairs (k_change.h) -- feature i is the cur half of pair i
+// with its base half's three properties
 static int gj_tiles(hm_ctx *ctx, const GjTexts &T, const GrowRec *recs, int64_t n, int32_t out_memory, const uint8_t **bytes,
-                    const int64_t **offsets, const double *dist_m = nullptr) {
+                    const int64_t **offsets, const double *dist_m = nullptr, bool pairs = false) {
     hm_ctx::GeoJson &G = ctx->gj;
     int rc;
     if ((rc = gj_init(ctx))) return rc;
@@ -102,7 +103,7 @@ static int gj_tiles(hm_ctx *ctx, const GjTexts &T, const GrowRec *recs, int64_t 
     HIPCHK(ctx, hipMemsetAsync(words, 0, GJW_WORDS * 8, ctx->stream));
     HIPCHK(ctx, hipEventRecord(G.ev[0], ctx->stream));
     hipLaunchKernelGGL(k_gj_tile_sizes, dim3(read_grid(ctx->read_grid, n, 256)), dim3(256), 0, ctx->stream, T, recs, n, vlat, vlng, (int *)G.vn.p,
-                       (unsigned *)G.sizes.p, words, dist_m);
+                       (unsigned *)G.sizes.p, words, dist_m, pairs ? 2 : 1, pairs);
     HIPCHK(ctx, hipEventRecord(G.ev[1], ctx->stream));
     gj_scan(ctx, n);
     HIPCHK(ctx, hipGetLastError());
@@ -110,16 +111,16 @@ static int gj_tiles(hm_ctx *ctx, const GjTexts &T, const GrowRec *recs, int64_t 
     HIPCHK(ctx, hipMemcpyAsync(&total, (unsigned long long *)G.off.p + n + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(&longest, words + GJW_MAX, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, ctx_sync(ctx, __LINE__));
-    const int tile_max = GJ_TILE_MAX + (dist_m ? GJ_DIST_MAX : 0);
+    const int tile_max = GJ_TILE_MAX + (dist_m ? GJ_DIST_MAX : 0) + (pairs ? GJ_BASE_MAX : 0);
     if (longest == 0 || longest > (unsigned long long)tile_max)
         return set_err(ctx, HM_E_STATE, "a tile feature of %llu bytes (at most %d expected)", longest, tile_max);
     const int64_t body_len = (int64_t)total + 1;
     if ((rc = ensure(ctx, G.bytes, (size_t)body_len + 16))) return rc;
-    const size_t lds = (size_t)GJ_THREADS * ((longest + 15) & ~15ull) + 64;   // (<= 64 x 912 + 64 B: below the 64-KB default)
+    const size_t lds = (size_t)GJ_THREADS * ((longest + 15) & ~15ull) + 64;   // (<= 64 x 992 + 64 B: below the 64-KB default)
     HIPCHK(ctx, hipEventRecord(G.ev[2], ctx->stream));
     hipLaunchKernelGGL(k_gj_tile_write, dim3(read_grid(ctx->read_grid, n, GJ_THREADS)), dim3(GJ_THREADS), lds, ctx->stream, T, recs, n,
                        (const double *)vlat, (const double *)vlng, (const int *)G.vn.p, (const unsigned long long *)G.off.p,
-                       (uint8_t *)G.bytes.p, dist_m);
+                       (uint8_t *)G.bytes.p, dist_m, pairs ? 2 : 1, pairs);
     HIPCHK(ctx, hipEventRecord(G.ev[3], ctx->stream));
     HIPCHK(ctx, hipGetLastError());
     return gj_out(ctx, n, body_len, out_memory, bytes, offsets);

@@ -23,9 +23,12 @@ int hm_live_windows(hm_ctx *ctx, int64_t *window_start_us, int64_t *keys, int64_
 // Leaves *m_out records of window window_start_us at res in ctx->ru_out (0: the window is not live); `who` names the
 // entry point in the errors (hm_window_rollup, and hm_window_geojson, which encodes the records where they are).
 // nslots_out (optional): the slots of the parent table in ctx->ru_tab, which stays probe-able until the next roll-up
-// (hm_window_raster looks the pixels' cells up there); 0 when the window is not live.
+// (hm_window_raster looks the pixels' cells up there; a change call, api_change.h, counts as one: it rolls its current
+// window up through ru_tab); 0 when the window is not live.
+// tab / out (optional): the parent table and the record buffer to use instead of ctx->ru_tab / ctx->ru_out (the change's
+// base window, api_change.h: its roll-up must survive the current window's).
 static int rollup_on_device(hm_ctx *ctx, int64_t window_start_us, int32_t res, const char *who, int64_t *m_out,
-                            int64_t *nslots_out = nullptr) {
+                            int64_t *nslots_out = nullptr, DevBuf *tab = nullptr, DevBuf *out = nullptr) {
     static_assert(sizeof(hm_state_rec) == sizeof(GrowRec), "hm_state_rec mirrors GrowRec");
     if (res < 0 || res > ctx->cfg.h3_res)
         return set_err(ctx, HM_E_INVALID, "roll-up resolution %d outside 0..%d", res, ctx->cfg.h3_res);
@@ -36,24 +39,25 @@ static int rollup_on_device(hm_ctx *ctx, int64_t window_start_us, int32_t res, c
     for (const auto &g : ctx->gens)
         if (g.wenc == wenc_of(window_start_us) && g.keys > 0) gen = &g;
     if (!gen) return HM_OK;
+    DevBuf &ru_tab = tab ? *tab : ctx->ru_tab, &ru_out = out ? *out : ctx->ru_out;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     // distinct parents possible: the window's keys, and the cells of the target resolution
     const int64_t bound = std::min(gen->keys, h3_cells_at(res));
     const int64_t nslots = (int64_t)next_pow2((uint64_t)std::max<int64_t>(2 * bound, 1024));
     int rc;
-    if ((rc = ensure(ctx, ctx->ru_tab, (size_t)nslots * sizeof(GrowRec))) ||
-        (rc = ensure(ctx, ctx->ru_out, (size_t)bound * sizeof(GrowRec))))
+    if ((rc = ensure(ctx, ru_tab, (size_t)nslots * sizeof(GrowRec))) ||
+        (rc = ensure(ctx, ru_out, (size_t)bound * sizeof(GrowRec))))
         return rc;
     unsigned long long *words = ctx->d_scratch + ROLLUP_WORD;   // parents emitted, overflow
-    HIPCHK(ctx, hipMemsetAsync(ctx->ru_tab.p, 0, (size_t)nslots * sizeof(GrowRec), ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ru_tab.p, 0, (size_t)nslots * sizeof(GrowRec), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(words, 0, 16, ctx->stream));
     const GenDesc d = gen_desc(*gen);
     // one workgroup per CU (its LDS table takes most of a CU's LDS), looping over the table
     const int grid = read_grid(ctx->read_grid, int64_t(1) << gen->log2cap, RU_THREADS * DUMP_PER, std::max(ctx->n_cus, 1));
-    hipLaunchKernelGGL(k_rollup, dim3(grid), dim3(RU_THREADS), 0, ctx->stream, d, (int)res, (GrowRec *)ctx->ru_tab.p,
+    hipLaunchKernelGGL(k_rollup, dim3(grid), dim3(RU_THREADS), 0, ctx->stream, d, (int)res, (GrowRec *)ru_tab.p,
                        (unsigned long long)(nslots - 1), words + 1);
     hipLaunchKernelGGL(k_rollup_emit, dim3(read_grid(ctx->read_grid, nslots, 256 * DUMP_PER)), dim3(256), 0, ctx->stream,
-                       (const GrowRec *)ctx->ru_tab.p, nslots, window_start_us, (GrowRec *)ctx->ru_out.p, bound, words);
+                       (const GrowRec *)ru_tab.p, nslots, window_start_us, (GrowRec *)ru_out.p, bound, words);
     HIPCHK(ctx, hipGetLastError());
     unsigned long long got[2] = {0, 0};
     HIPCHK(ctx, hipMemcpyAsync(got, words, 16, hipMemcpyDeviceToHost, ctx->stream));

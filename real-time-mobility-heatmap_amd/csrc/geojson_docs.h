@@ -27,8 +27,11 @@ constexpr int GJ_TEXT_MAX = 40;      // a window text
 constexpr int GJ_PREFIX_LEN = 40;    // {"type":"FeatureCollection","features":[
 #define HM_GJ_PREFIX "{\"type\":\"FeatureCollection\",\"features\":["
 // the longest tile feature: 63 + 11 x 51 + 10 + 18 + 27 + 29 + 39 + 57 + 55 + 2 bytes, and its separator; with the near's
-// distance (,"distanceM": and at most 24 bytes of number) GJ_DIST_MAX more
+// distance (,"distanceM": and at most 24 bytes of number) GJ_DIST_MAX more; with the change's base
+// (,"baseCount": ,"baseAvgSpeedKmh": ,"countChange": -- 13 + 19 + 15 bytes -- and at most 20 + 24 + 20 bytes of numbers)
+// GJ_BASE_MAX more
 constexpr int GJ_DIST_MAX = 38;
+constexpr int GJ_BASE_MAX = 111;
 constexpr int GJ_TILE_MAX = 872;
 
 // the two window texts of a call, by value (a kernel argument)
@@ -113,11 +116,21 @@ struct JsonW {
     }
 };
 
+// the base half of a change pair, as tile_feature appends it
+struct GjBase {
+    int64_t count, n_speed;
+    double sum_speed;
+};
+
 // one tile feature from the record's fields and its boundary (vertex k at lat[k * stride], lng[k * stride]); returns
 // its length (without the separator that follows it in the body).  dist_m (optional): the record's distance from a near
-// query's point, appended as the last property ,"distanceM":<repr>; nullptr: the feature as it always was
+// query's point, appended as the last property ,"distanceM":<repr>; nullptr: the feature as it always was.  base
+// (optional): the cell's record in a change's base window, appended after windowEnd as
+// ,"baseCount":<int>,"baseAvgSpeedKmh":<repr>,"countChange":<int> (the average by avgSpeedKmh's rule, the change
+// count - base count as int64); nullptr: every byte as without it
 HM_HD int tile_feature(uint8_t *dst, const GjTexts &T, uint64_t cell, int64_t count, int64_t n_speed, double sum_speed,
-                       int nv, const double *lat, const double *lng, int64_t stride, const double *dist_m = nullptr) {
+                       int nv, const double *lat, const double *lng, int64_t stride, const double *dist_m = nullptr,
+                       const GjBase *base = nullptr) {
     JsonW w{dst, 0};
     w.lit("{\"type\":\"Feature\",\"geometry\":{\"type\":\"Polygon\",\"coordinates\":[[");
     for (int k = 0; k < nv; k++) {
@@ -149,6 +162,14 @@ HM_HD int tile_feature(uint8_t *dst, const GjTexts &T, uint64_t cell, int64_t co
     w.lit("\",\"windowEnd\":\"");
     w.bytes(T.end, T.end_len);
     w.u8('"');
+    if (base) {
+        w.lit(",\"baseCount\":");
+        w.i64(base->count);
+        w.lit(",\"baseAvgSpeedKmh\":");
+        w.f64(base->n_speed == 0 ? 0.0 : base->sum_speed / (double)base->n_speed);
+        w.lit(",\"countChange\":");
+        w.i64(count - base->count);
+    }
     if (dist_m) {
         w.lit(",\"distanceM\":");
         w.f64(*dist_m);

@@ -274,6 +274,18 @@ struct hm_ctx {
         int tot_zones = 0;        // the zones whose totals the last scan left in h_tot (0: it did not run)
         int64_t info[6] = {0, 0, 0, 0, 0, 0};   // hm_within_info
     } within;
+    // hm_window_change* (api_change.h, k_change.h): the base window's roll-up (its parent table, whose touched words the
+    // join marks, and its records -- not ru_tab / ru_out, which take the current window's), the pairs, those in view,
+    // those in rank order, the control words -- buffers of its own (the ranking borrows the top's key buffers and
+    // scratch as the near path does).  Nothing here is allocated before the first call.
+    struct Change {
+        DevBuf tab, recs, out, vout, ranked, words;
+        void *h_out = nullptr;    // pinned host copy of the pairs
+        size_t h_out_cap = 0;
+        hipEvent_t ev[4] = {};    // around the join's kernels; around the view's k_view_tiles
+        bool ready = false;
+        int64_t info[6] = {0, 0, 0, 0, 0, 0};   // hm_change_info
+    } change;
     DevBuf keys;                    // k_ingest's event key per row (kernels.h ekey)
     // k_ingest's fused binning (large direct-path batches): the bins' cursors (RP_BINS + 1 u32: the last stays 0, so
     // that their exclusive scan ends with the total) and the slab capacity; the slabs are parts_sorted
@@ -449,6 +461,14 @@ static void within_free(hm_ctx *ctx) {
     for (void *h : {W.h_zones, W.h_out, W.h_zone, W.h_tot})
         if (h) (void)hipHostFree(h);
     for (auto &e : W.ev)
+        if (e) (void)hipEventDestroy(e);
+}
+static void change_free(hm_ctx *ctx) {
+    hm_ctx::Change &C = ctx->change;
+    for (DevBuf *b : {&C.tab, &C.recs, &C.out, &C.vout, &C.ranked, &C.words})
+        if (b->p) (void)hipFree(b->p);
+    if (C.h_out) (void)hipHostFree(C.h_out);
+    for (auto &e : C.ev)
         if (e) (void)hipEventDestroy(e);
 }
 

@@ -98,8 +98,12 @@ __global__ __launch_bounds__(256) void k_cells_in_view(const uint64_t *__restric
 // (room for n); *n_out counts them.  A thread tests its DUMP_PER records of the iteration one after the other (one copy
 // of the boundary code) and keeps the verdicts as bits; block256_compact then asks the same thread for the same records.
 // No reject ahead of the exact boundary: none was proved never to drop a tile the rule keeps.
-__global__ __launch_bounds__(256) void k_view_tiles(const GrowRec *__restrict__ recs, int64_t n, uint64_t north_pole,
-                                                    uint64_t south_pole, hm_view v, GrowRec *__restrict__ out,
+// Rec: the record kept whole, GrowRec (every caller but one) or the change's pair of them (k_change.h); rec_cell gives
+// its cell.
+HM_HD uint64_t rec_cell(const GrowRec &r) { return r.cell; }
+template <class Rec = GrowRec>
+__global__ __launch_bounds__(256) void k_view_tiles(const Rec *__restrict__ recs, int64_t n, uint64_t north_pole,
+                                                    uint64_t south_pole, hm_view v, Rec *__restrict__ out,
                                                     unsigned long long *n_out) {
     const int64_t tile = 256 * DUMP_PER;
     for (int64_t base = (int64_t)blockIdx.x * tile; base < n; base += (int64_t)gridDim.x * tile) {
@@ -107,7 +111,7 @@ __global__ __launch_bounds__(256) void k_view_tiles(const GrowRec *__restrict__ 
 #pragma unroll 1
         for (int k = 0; k < DUMP_PER; k++) {
             const int64_t i = base + k * 256 + threadIdx.x;
-            if (i < n && cell_in_view(recs[i].cell, c_tab, north_pole, south_pole, v)) bits |= 1u << k;
+            if (i < n && cell_in_view(rec_cell(recs[i]), c_tab, north_pole, south_pole, v)) bits |= 1u << k;
         }
         const auto is_live = [=](int64_t i) { return ((bits >> (unsigned)((i - base) >> 8)) & 1u) != 0; };
         block256_compact<true>(base, is_live, n_out, (unsigned long long)n,

@@ -239,6 +239,13 @@ SIGNATURES = {
     "hm_selftest_positions_within": (c_i32, [_P(HmZones), c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, _P(c_i64)]),
     "hm_selftest_tiles_within": (c_i32, [_P(HmZones), c_vp, c_i64, c_vp, c_vp, c_vp, _P(c_i64)]),
     "hm_within_info": (c_i32, [c_vp, c_vp, c_i32]),
+    "hm_window_change": (c_i32, [c_vp, c_i64, c_i64, c_i32, _P(HmView), c_i32, _P(c_vp), _P(c_i64)]),
+    "hm_window_change_top": (c_i32, [c_vp, c_i64, c_i64, c_i32, _P(HmView), c_i32, c_i64, c_i32, _P(c_vp), _P(c_i64)]),
+    "hm_window_geojson_change": (c_i32, [c_vp, c_i64, c_i64, c_i32, _P(HmGeojsonCfg), _P(HmView), c_i32, c_i64, c_i32, _P(c_vp),
+                                         _P(c_vp), _P(c_i64), _P(c_vp)]),
+    "hm_selftest_window_change": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i32, c_i64, c_vp, _P(c_i64)]),
+    "hm_selftest_change_features": (c_i32, [_P(HmGeojsonCfg), c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "hm_change_info": (c_i32, [c_vp, c_vp, c_i32]),
     "hm_test_read_grid_info": (c_i32, [c_vp, c_vp, c_vp, c_vp]),
     "hm_selftest_float_repr_host": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "hm_selftest_float_repr_device": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32]),
@@ -759,6 +766,59 @@ def state_recs_at(p, n, copy=True):
         return np.zeros(0, STATE_REC_DTYPE)
     recs = np.ctypeslib.as_array(ctypes.cast(p, _P(ctypes.c_uint8)), shape=(n * STATE_REC_DTYPE.itemsize,)).view(STATE_REC_DTYPE)
     return recs.copy() if copy else recs
+
+
+# ---- change between two live windows (csrc/k_change.h) ----
+HM_CHANGE_RISING, HM_CHANGE_FALLING, HM_CHANGE_ABS = 0, 1, 2
+CHANGE_ORDERS = {"rising": HM_CHANGE_RISING, "falling": HM_CHANGE_FALLING, "abs": HM_CHANGE_ABS}
+# hm_change_rec (128 B): a cell's record in the current window and in the base window
+CHANGE_REC_DTYPE = np.dtype([("cur", STATE_REC_DTYPE), ("base", STATE_REC_DTYPE)])
+assert CHANGE_REC_DTYPE.itemsize == 128
+
+
+def change_order_code(order):
+    """HM_CHANGE_* of "rising" / "falling" / "abs" (or of the code itself); ValueError otherwise."""
+    if isinstance(order, str) and order in CHANGE_ORDERS:
+        return CHANGE_ORDERS[order]
+    if not isinstance(order, str) and int(order) in CHANGE_ORDERS.values():
+        return int(order)
+    raise ValueError(f"order {order!r} is none of {sorted(CHANGE_ORDERS)}")
+
+
+def change_recs_at(p, n, copy=True):
+    """n hm_change_rec at host pointer p as a CHANGE_REC_DTYPE array (a copy, or a view of the library's buffer)."""
+    if n == 0:
+        return np.zeros(0, CHANGE_REC_DTYPE)
+    recs = np.ctypeslib.as_array(ctypes.cast(p, _P(ctypes.c_uint8)), shape=(n * CHANGE_REC_DTYPE.itemsize,)).view(CHANGE_REC_DTYPE)
+    return recs.copy() if copy else recs
+
+
+def window_change_selftest(cur, base, window_start_us, base_start_us, order=None, k=None):
+    """Host execution of the change's join, key and ordering (no GPU) on two STATE_REC_DTYPE arrays: every pair sorted by
+    cell (order None), or the first min(k, n) pairs of the order (k None: HM_TOP_MAX)."""
+    lib = load()
+    cur = np.ascontiguousarray(cur, dtype=STATE_REC_DTYPE)
+    base = np.ascontiguousarray(base, dtype=STATE_REC_DTYPE)
+    kk = -1 if order is None else HM_TOP_MAX if k is None else int(k)
+    out = np.zeros(max(cur.size + base.size, 1), CHANGE_REC_DTYPE)
+    n = c_i64()
+    check(lib.hm_selftest_window_change(ptr(cur) if cur.size else None, cur.size, ptr(base) if base.size else None, base.size,
+                                        int(window_start_us), int(base_start_us), 0 if order is None else change_order_code(order), kk,
+                                        ptr(out), ctypes.byref(n)), None, "hm_selftest_window_change")
+    return out[:n.value].copy()
+
+
+def change_features_selftest(pairs, window_start_text, window_end_text):
+    """Host execution of the GPU encoder on CHANGE_REC_DTYPE pairs (no GPU): (body uint8, offsets int64)."""
+    lib = load()
+    pairs = np.ascontiguousarray(pairs, dtype=CHANGE_REC_DTYPE)
+    cfg, keep = geojson_cfg(window_start_text, window_end_text)
+    cap = 64 + 1040 * pairs.size
+    buf = np.zeros(cap, np.uint8)
+    offs = np.zeros(pairs.size + 1, np.int64)
+    check(lib.hm_selftest_change_features(ctypes.byref(cfg), ptr(pairs) if pairs.size else None, pairs.size, ptr(buf), cap, ptr(offs)),
+          None, "hm_selftest_change_features")
+    return buf[:geojson_body_len(offs)].copy(), offs
 
 
 # ---- radius queries (csrc/k_near.h) ----

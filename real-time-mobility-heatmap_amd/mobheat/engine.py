@@ -744,6 +744,72 @@ class HeatmapEngine:
         return {"candidates": v[0], "returned": v[1], "count_passes": v[2], "cell_passes": v[3], "index_passes": v[4],
                 "tied": v[5], "device_us": v[6]}
 
+    # ---- change between two live windows: rising and falling tiles (hm_window_change*; csrc/k_change.h) ----
+    def _change_windows(self, window_start_us, base_start_us):
+        if window_start_us is None:
+            ws, _ = self.live_windows()
+            window_start_us = ws[-1] if ws.size else 0
+        window_start_us = int(window_start_us)
+        return window_start_us, window_start_us - self.tile_us if base_start_us is None else int(base_start_us)
+
+    def window_change(self, window_start_us=None, base_start_us=None, res=None, view=None, order=None, k=None, copy=True):
+        """The tiles of live window window_start_us (None: the newest) against those of base_start_us (None: the window
+        before it) at resolution res <= h3_res (None: h3_res): CHANGE_REC_DTYPE pairs, one per cell of either window --
+        `cur` the record window_records returns for the cell in the window, `base` the one of the base window, a window
+        without the cell (or not live) giving a zero record; countChange = cur.count - base.count.  Both windows are
+        rolled up and joined on the GPU in one call (hm_window_change), in no particular order.  view=(west, south,
+        east, north): only the cells in view.  order="rising" / "falling" / "abs" with k (None: 65536): the first k
+        pairs by countChange descending / ascending / |countChange| descending, ties by cell ascending, in rank order
+        (hm_window_change_top).  copy=False: a view of the library's pinned buffer, valid until the next call on this
+        engine.  On a shard engine: the rank's own cells, unranked only."""
+        res = self.h3_res if res is None else int(res)
+        ws, bs = self._change_windows(window_start_us, base_start_us)
+        v = None if view is None else _lib.view_struct(view)
+        vp = None if v is None else ctypes.byref(v)
+        p, n = ctypes.c_void_p(), ctypes.c_int64()
+        if order is None:
+            if k is not None:
+                raise ValueError("k needs an order")
+            check(self._lib.hm_window_change(self._ctx, ws, bs, res, vp, HM_MEM_HOST, ctypes.byref(p), ctypes.byref(n)),
+                  self._ctx, "hm_window_change")
+        else:
+            check(self._lib.hm_window_change_top(self._ctx, ws, bs, res, vp, _lib.change_order_code(order),
+                                                 _lib.HM_TOP_MAX if k is None else int(k), HM_MEM_HOST, ctypes.byref(p),
+                                                 ctypes.byref(n)), self._ctx, "hm_window_change_top")
+        return _lib.change_recs_at(p, n.value, copy)
+
+    def window_change_geojson(self, window_start_us=None, base_start_us=None, res=None, view=None, order=None, k=None, tz=None,
+                              copy=True, with_records=False):
+        """window_change's pairs as the body of a /api/tiles/change route: window_geojson's feature of every pair's cur
+        half with baseCount, baseAvgSpeedKmh and countChange after windowEnd, encoded on the GPU where the pairs lie
+        (hm_window_geojson_change) -- json.dumps(readside.tiles_change_from_engine(...), separators=(",", ":")).
+        with_records: (body, pairs in feature order, offsets) instead."""
+        res = self.h3_res if res is None else int(res)
+        ws, bs = self._change_windows(window_start_us, base_start_us)
+        if order is None and k is not None:
+            raise ValueError("k needs an order")
+        cfg, keep = _lib.geojson_cfg(_lib.wall_iso(ws, tz), _lib.wall_iso(ws + self.tile_us, tz))
+        v = None if view is None else _lib.view_struct(view)
+        pb, po, pr, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        kk = -1 if order is None else _lib.HM_TOP_MAX if k is None else int(k)
+        if order is not None and kk < 0:
+            raise ValueError(f"k = {kk} outside 0..{_lib.HM_TOP_MAX}")
+        check(self._lib.hm_window_geojson_change(self._ctx, ws, bs, res, ctypes.byref(cfg), None if v is None else ctypes.byref(v),
+                                                 0 if order is None else _lib.change_order_code(order), kk, HM_MEM_HOST,
+                                                 ctypes.byref(pb), ctypes.byref(po), ctypes.byref(n),
+                                                 ctypes.byref(pr) if with_records else None),
+              self._ctx, "hm_window_geojson_change")
+        body = self._geojson_body(pb, po, n.value, copy)
+        if not with_records:
+            return body
+        offs = np.ctypeslib.as_array(ctypes.cast(po, ctypes.POINTER(ctypes.c_int64)), shape=(n.value + 1,)).copy()
+        return body, _lib.change_recs_at(pr, n.value), offs
+
+    def change_info(self):
+        v = (ctypes.c_int64 * 6)()
+        check(self._lib.hm_change_info(self._ctx, v, 6), self._ctx, "hm_change_info")
+        return {"cur_cells": v[0], "base_cells": v[1], "both": v[2], "in_view": v[3], "returned": v[4], "device_us": v[5]}
+
     # ---- radius queries: the vehicles / tiles nearest a point (hm_*_near; csrc/k_near.h) ----
     def positions_near(self, lat, lon, max_distance_m=float("inf"), k=_lib.HM_TOP_MAX, since_us=None, copy=True):
         """The k vehicles of the positions state nearest (lat, lon) within max_distance_m metres (closed; inf: no limit),

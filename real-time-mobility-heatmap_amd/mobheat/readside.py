@@ -393,6 +393,89 @@ def tiles_top_from_engine(engine, k, res=None, city="boston", tz=None, view=None
     return _top_features(tiles_latest_from_engine(engine, res, city, tz, view), k)
 
 
+# ---- change between two live windows: rising and falling tiles (HeatmapEngine.window_change, csrc/k_change.h) ----
+def change_of(cur_records, base_records, window_start_us, base_start_us):
+    """change(A, B) in numpy from the two windows' STATE_REC_DTYPE records (cells distinct within each): one
+    CHANGE_REC_DTYPE pair per cell of either, sorted by cell -- `cur` / `base` the window's record of the cell, whole, or
+    the zero record {cell, that window's start, 0, ...} where it has none.  The comparison form of
+    HeatmapEngine.window_change."""
+    cur = np.asarray(cur_records, dtype=_lib.STATE_REC_DTYPE)
+    base = np.asarray(base_records, dtype=_lib.STATE_REC_DTYPE)
+    if int(window_start_us) == int(base_start_us):
+        raise ValueError("the window and its base are the same window")
+    cells = np.union1d(cur["cell"], base["cell"])
+    out = np.zeros(cells.size, _lib.CHANGE_REC_DTYPE)
+    for half, recs, ws in (("cur", cur, window_start_us), ("base", base, base_start_us)):
+        h = out[half]   # (a view)
+        h["cell"] = cells
+        h["window_start_us"] = int(ws)
+        h[np.searchsorted(cells, recs["cell"])] = recs
+    return out
+
+
+def change_order(change, cell, order, k):
+    """The input indices of the first min(k, n) pairs in a change order: "rising" countChange descending, "falling"
+    ascending, "abs" |countChange| descending; then cell ascending as uint64, then input index."""
+    change, cell = np.asarray(change).astype(np.int64), np.asarray(cell).astype(np.uint64)
+    k = int(k)
+    if not 0 <= k <= TOP_MAX:
+        raise ValueError(f"k = {k} outside 0..{TOP_MAX}")
+    code = _lib.change_order_code(order)
+    primary = -change if code == _lib.HM_CHANGE_RISING else change if code == _lib.HM_CHANGE_FALLING else -np.abs(change)
+    return np.lexsort((np.arange(change.size), cell, primary))[:k]
+
+
+def change_top_of(pairs, order, k=TOP_MAX):
+    """the first min(k, n) CHANGE_REC_DTYPE pairs of the order, whole: the comparison form of window_change(order=, k=)"""
+    pairs = np.asarray(pairs, dtype=_lib.CHANGE_REC_DTYPE)
+    return pairs[change_order(pairs["cur"]["count"] - pairs["base"]["count"], pairs["cur"]["cell"], order, k)]
+
+
+def tiles_change_collection(pairs, window_start, window_end, device=0):
+    """The FeatureCollection of CHANGE_REC_DTYPE pairs, in their order: tiles_latest_collection's feature of every cur
+    half (windowStart / windowEnd: the two datetimes given) with baseCount, baseAvgSpeedKmh and countChange after
+    windowEnd."""
+    pairs = np.asarray(pairs, dtype=_lib.CHANGE_REC_DTYPE)
+
+    def avg(r):
+        return float(r["sum_speed"] / r["n_speed"]) if r["n_speed"] else 0.0
+    docs = [{"cellId": format(int(p["cur"]["cell"]), "x"), "count": int(p["cur"]["count"]), "avgSpeedKmh": avg(p["cur"]),
+             "windowStart": window_start, "windowEnd": window_end} for p in pairs]
+    fc = tiles_latest_collection(docs, device)
+    for f, p in zip(fc["features"], pairs):
+        f["properties"]["baseCount"] = int(p["base"]["count"])
+        f["properties"]["baseAvgSpeedKmh"] = avg(p["base"])
+        f["properties"]["countChange"] = int(p["cur"]["count"]) - int(p["base"]["count"])
+    return fc
+
+
+def tiles_change_from_engine(engine, window_start_us=None, base_start_us=None, res=None, view=None, order=None, k=None, tz=None):
+    """The FeatureCollection a /api/tiles/change?res=&bbox=&order=&n= route returns, built here from two window_records
+    calls: change_of, the view (cells_in_view), the order (change_top_of).  Without an order the features are sorted by
+    cell.  The comparison form of tiles_change_body."""
+    import datetime as _dt
+
+    from .stream import _spark_datetime
+
+    def when(us):
+        if tz is None:
+            return _spark_datetime(us)
+        return _dt.datetime.fromtimestamp(us // 1000000, tz).replace(tzinfo=None, microsecond=us % 1000000)
+    ws, bs = engine._change_windows(window_start_us, base_start_us)
+    pairs = change_of(engine.window_records(ws, res), engine.window_records(bs, res), ws, bs)
+    if view is not None:
+        pairs = pairs[cells_in_view(pairs["cur"]["cell"], view, engine.device)]
+    if order is not None:
+        pairs = change_top_of(pairs, order, TOP_MAX if k is None else k)
+    return tiles_change_collection(pairs, when(ws), when(ws + engine.tile_us), engine.device)
+
+
+def tiles_change_body(engine, window_start_us=None, base_start_us=None, res=None, view=None, order=None, k=None, tz=None):
+    """The response body of a /api/tiles/change route as bytes, rolled up, joined, ranked and encoded on the GPU in one call
+    (HeatmapEngine.window_change_geojson); without an order the features come in the join's order, not sorted."""
+    return engine.window_change_geojson(window_start_us, base_start_us, res, view, order, k, tz)
+
+
 # ---- radius queries: what is around a point, nearest first (HeatmapEngine.positions_near / window_near, csrc/k_near.h) ----
 EARTH_RADIUS_M = _lib.HM_EARTH_RADIUS_M   # MongoDB's sphere
 _DEG = 0.017453292519943295               # the double math.radians multiplies by
