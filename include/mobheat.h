@@ -280,16 +280,26 @@ int hm_state_export_touched(hm_ctx *ctx, hm_state_info *info, hm_state_rec *recs
  * *n_out; _copy writes records [first, first + count) of that dump to host memory `recs` (page-locked memory: the
  * copy runs at the link's rate).  _copy may run on another thread while hm_encode_tile_updates /
  * hm_encode_position_updates run on this context (it uses a stream of its own), never beside hm_process_batch, a
- * stage call or another export; a batch or another export in between makes it fail (HM_E_STATE). */
+ * stage call or another export.  A _copy / _copy_async CALLED after a batch, or after another export that rewrote the
+ * dump, fails (HM_E_STATE): the dump it names is gone. */
 int hm_state_export_begin(hm_ctx *ctx, hm_state_info *info, int32_t touched_only, int64_t *n_out);
 int hm_state_export_copy(hm_ctx *ctx, hm_state_rec *recs, int64_t first, int64_t count);
 /* _copy split in two: _async enqueues the copy and marks its completion in slot (0..63) -- call it on the engine's
  * thread BEFORE the statements' encode, so that the encode's copies queue behind it, not the other way round -- and
- * _wait (any thread) blocks until the copy marked in slot has landed. */
+ * _wait (any thread) blocks until the copy marked in slot has landed.
+ * A copy that _async has queued is safe against what the context does next: hm_process_batch, a stage call,
+ * hm_state_export, hm_state_export_touched, hm_state_export_begin and hm_state_import make their stream wait for the
+ * last queued copy before they rewrite or reallocate the dump, so a slice waited for only afterwards still holds the
+ * records of the dump it was queued from (and _wait still returns HM_OK).  What the caller owes is `recs`: it must stay
+ * valid until _wait has returned for the slot, and a slot is reused only after its _wait. */
 int hm_state_export_copy_async(hm_ctx *ctx, hm_state_rec *recs, int64_t first, int64_t count, int32_t slot);
 int hm_state_export_copy_wait(hm_ctx *ctx, int32_t slot);
 /* Restores an exported state into a context that has processed no batch (HM_E_STATE otherwise); the
- * config fields of info must equal the context's (HM_E_INVALID). recs: info->n_keys distinct keys, host memory. */
+ * config fields of info must equal the context's (HM_E_INVALID). recs: info->n_keys distinct keys, host memory, in any
+ * order.  Refused with HM_E_INVALID: a record with a zero cell, reserved != 0, count < 1, n_speed outside [0, count] or
+ * a window_start_us that is no window start; a cell that is not an H3 cell (mode 1) of the context's h3_res; on a shard
+ * context a key another rank owns; a (cell, window_start_us) key given twice.  Refused with HM_E_OVERFLOW: more than
+ * 2048 windows.  A refused import leaves the context as it was: fresh, and free to import again. */
 int hm_state_import(hm_ctx *ctx, const hm_state_info *info, const hm_state_rec *recs);
 
 /* Tiles of the last batch as MongoDB update statements (reference heatmap_stream.py:164-196): statement i is

@@ -50,6 +50,7 @@ int hm_create(const hm_config *cfg, hm_ctx **out) {
         if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { ctx->err = "event"; return fail("create"); }
     for (auto &e : ctx->export_ev)
         if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { ctx->err = "event"; return fail("create"); }
+    if (hipEventCreateWithFlags(&ctx->export_fence, hipEventDisableTiming) != hipSuccess) { ctx->err = "event"; return fail("create"); }
     for (auto &e : ctx->stm_ev)
         if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { ctx->err = "event"; return fail("create"); }
     // k_merge_owned's resident tags live in dynamic LDS of up to MO_TAG_MAX bytes (merge_sorted)
@@ -294,6 +295,7 @@ void hm_destroy(hm_ctx *ctx) {
     if (ctx->copy_stream) (void)hipStreamSynchronize(ctx->copy_stream);
     for (auto &e : ctx->export_ev)
         if (e) (void)hipEventDestroy(e);
+    if (ctx->export_fence) (void)hipEventDestroy(ctx->export_fence);
     for (auto &e : ctx->stm_ev)
         if (e) (void)hipEventDestroy(e);
     if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);

@@ -96,6 +96,8 @@ struct hm_ctx {
     int64_t stm_piece = 0, stm_total = 0;
     static constexpr int EXPORT_SLICES = 64;
     hipEvent_t export_ev[EXPORT_SLICES] = {};   // hm_state_export_copy_async: slice k landed
+    hipEvent_t export_fence = nullptr;   // behind the last export copy queued on copy_stream (export_copies_fence)
+    bool export_fence_pending = false;   // ... and not yet waited for by ctx->stream
     DevBuf parts_regrow_sorted;       // growth: the same, partitioned (not parts_sorted: a binned batch's slabs are there)
     // multi-GPU exchange (api_stage.h): chunk starts and headers, the local -> global window slot map; the owner's
     // per-sender bin counts and their scan, its bins' segments, the received candidates and table-mode partials
@@ -577,6 +579,17 @@ static int ensure(hm_ctx *ctx, DevBuf &b, size_t bytes) {
         }
     }
     b.bytes = want;
+    return HM_OK;
+}
+
+// hm_state_export_copy_async's copies read parts_regrow on copy_stream.  Whoever writes or reallocates that buffer next
+// (state_dump, hm_state_export_touched's dump, gens_prepare's regrow, hm_state_import) first makes ctx->stream wait for
+// the last copy queued: a batch or an export started before every slice was waited for leaves those slices as the
+// dump they were queued from.  ensure()'s reallocation drains ctx->stream, and with it this wait.
+static int export_copies_fence(hm_ctx *ctx) {
+    if (!ctx->export_fence_pending) return HM_OK;
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->export_fence, 0));
+    ctx->export_fence_pending = false;
     return HM_OK;
 }
 
@@ -1101,6 +1114,7 @@ static int gens_prepare(hm_ctx *ctx, const std::vector<WinCount> &census, bool r
         for (const auto &g : old) moved += g.keys;
         ctx->touched_dump_seq = -1;
         ctx->bin_offsets_ready = false;   // (the regrow's partition below writes rp_O)
+        if ((rc = export_copies_fence(ctx))) return rc;   // (export copies still queued read parts_regrow)
         if ((rc = ensure(ctx, ctx->parts_regrow, std::max<int64_t>(moved, 1) * sizeof(GrowRec)))) return rc;
         HIPCHK(ctx, hipMemsetAsync(ctx->d_scratch + REGROW_WORD, 0, 8, ctx->stream));
         ctx->touched_dump_seq = ctx->export_dump_n = -1;   // (parts_regrow is overwritten)
