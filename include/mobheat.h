@@ -36,6 +36,8 @@
  *   hm_window_raster             -- a live window's counts per pixel of a grid, for z/x/y raster tiles of the heatmap.
  *   hm_positions_density*        -- the positions state grouped into H3 cells: vehicles per cell at any resolution.
  *   hm_*_near / hm_*_within      -- what is around a point (radius queries) and what is inside polygon zones (geofences).
+ *   hm_window_change* / hm_span_* -- two live windows against each other, and a trailing span of them as one heatmap
+ *                                   with every cell's count per window ("the last 15 minutes").
  */
 #ifndef MOBHEAT_H
 #define MOBHEAT_H
@@ -944,6 +946,54 @@ int hm_selftest_change_features(const hm_geojson_cfg *cfg, const hm_change_rec *
  * after the view, [4] pairs returned, [5] device microseconds of the change's own kernels (HIP events around the join,
  * the view and the ranking; the two roll-ups excluded).  All 0 before the first call. */
 int hm_change_info(const hm_ctx *ctx, int64_t *v, int32_t n);
+
+/* ---- a trailing span of live windows as one heatmap, with every cell's count per window ("the last 15 minutes") ----
+ * span(end_start_us, windows, r): the `windows` consecutive tumbling windows whose starts are first = end_start_us -
+ * (windows - 1) * tile_us, ..., end_start_us; 1 <= windows <= HM_SPAN_MAX_WINDOWS, end_start_us a multiple of tile_us
+ * (HM_E_INVALID otherwise), 0 <= r <= h3_res.  A window of the span that is not live contributes nothing and is no error;
+ * no live window: *n = 0.  The records are hm_state_recs, one per parent cell at r that any of the windows holds, in no
+ * particular order: count, n_speed and the three sums added up over the windows and the children (counts and n_speed
+ * exact; the sums fp64 additions in no fixed order, as hm_window_rollup's), window_start_us = first, reserved = 0.
+ * series: int64[*n][windows], row i record i's, column j the cell's count in window first + j * tile_us (0 where the
+ * window or the cell is absent); the row adds up to the record's count.  All selected windows' tables are aggregated
+ * in one launch (csrc/k_span.h).
+ * view (NULL: none) keeps a record iff hm_window_geojson_view's rule keeps its cell; k >= 0: the first min(k, n) records
+ * of hm_top_records' order (k <= HM_TOP_MAX), after the view; k < 0: unranked.  The rows follow their records.
+ * Outputs are library-owned, in device or pinned host memory per out_memory, valid until the next call on the context.
+ * A span call counts as a roll-up for hm_window_rollup's buffers (as a change call does): its parent table is what
+ * hm_span_raster looks the pixels up in.  The calls read the tile state only (hm_state_version, an export in progress
+ * are unaffected); a repeated identical call allocates nothing.  Checks in hm_window_top's order: the arguments, the
+ * resolution, the shard, the stage.  On a shard context the unranked records are the rank's partial (add the records
+ * and rows of equal cell across ranks); ranked calls and hm_span_raster: HM_E_UNSUPPORTED -- for the raster that is
+ * stricter than hm_window_raster, which allows counts on a shard and refuses only classes (HM_E_INVALID): a rank's
+ * per-window grids still add up to the span's.  A parent-table overflow: HM_E_OVERFLOW. */
+#define HM_SPAN_MAX_WINDOWS 16
+int hm_span_rollup(hm_ctx *ctx, int64_t end_start_us, int32_t windows, int32_t res, const hm_view *view /* NULL: no filter */,
+                   int64_t k /* < 0: unranked */, int32_t out_memory, const hm_state_rec **recs, const int64_t **series, int64_t *n);
+/* the same records as a FeatureCollection: hm_window_geojson's feature of record i (cfg's texts: windowStart = first,
+ * windowEnd = end_start_us + tile_us) with ,"windows":<windows>,"counts":[c0,...] -- row i -- after windowEnd.  Body,
+ * offsets and *n as hm_window_geojson's; nothing selected: the 42-byte empty body.  A feature may be up to 1232 bytes
+ * with its series; the encoder's workgroup holds features of at most 1008, so a call whose longest feature is longer
+ * (counts of 13 and more digits in most of 16 windows: no real count) fails with HM_E_UNSUPPORTED, nothing returned. */
+int hm_span_geojson(hm_ctx *ctx, int64_t end_start_us, int32_t windows, int32_t res, const hm_geojson_cfg *cfg,
+                    const hm_view *view /* NULL: no filter */, int64_t k /* < 0: unranked */, int32_t out_memory,
+                    const uint8_t **bytes, const int64_t **offsets, int64_t *n);
+/* hm_window_raster of the span's summed counts: its grid, thresholds, limits, classes, outputs and buffers */
+int hm_span_raster(hm_ctx *ctx, int64_t end_start_us, int32_t windows, int32_t res, const double *lat, int32_t rows,
+                   const double *lon, int32_t cols, const int64_t *thresholds, int32_t n_thresholds, int32_t out_memory,
+                   const uint32_t **counts, const uint8_t **classes);
+/* up to n of, for the last span call on the context: [0] live windows used, [1] their keys (scanned), [2] parents,
+ * [3] records kept by the view, [4] records returned, [5] parent-table slots, [6] device microseconds of the span's
+ * kernels (HIP events around the aggregation, the view, the ranking and the rows).  All 0 before the first call. */
+int hm_span_info(const hm_ctx *ctx, int64_t *v, int32_t n);
+/* Host execution (no GPU) over per-window record arrays at any resolutions >= res: recs holds window j's n_per_window[j]
+ * records after those of the windows before it (window j = first_us + j * tile_us).  out: room for all of them; series:
+ * int64[that many][windows]; the records come sorted by cell, the sums added in input order. */
+int hm_selftest_span(const hm_state_rec *recs, const int64_t *n_per_window, int32_t windows, int64_t first_us, int64_t tile_us,
+                     int32_t res, hm_state_rec *out, int64_t *series, int64_t *n_out);
+/* host execution of the encoder on n records and their rows, as hm_selftest_tile_features */
+int hm_selftest_span_features(const hm_geojson_cfg *cfg, const hm_state_rec *recs, const int64_t *series, int32_t windows,
+                              int64_t n, uint8_t *bytes, int64_t cap, int64_t *offsets);
 
 /* Tests: MOBHEAT_TEST_READ_GRID=<G>, read at hm_create (and by every hm_cells_in_view / hm_points_in_zones on a device),
  * runs the streaming kernels of the read side (view, roll-up, density, within, raster, GeoJSON, positions export), of the

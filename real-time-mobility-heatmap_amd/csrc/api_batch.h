@@ -264,6 +264,7 @@ void hm_destroy(hm_ctx *ctx) {
     near_free(ctx);
     within_free(ctx);
     change_free(ctx);
+    span_free(ctx);
     for (auto &g : ctx->gens)
         if (!in_arena(ctx, g.tab)) (void)hipFree(g.tab);
     for (auto &pt : ctx->pool)

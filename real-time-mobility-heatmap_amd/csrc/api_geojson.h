@@ -87,9 +87,11 @@ static int gj_out(hm_ctx *ctx, int64_t n, int64_t body_len, int32_t out_memory, 
 
 // the features of n device records: sizes -> scan -> write -> out.  dist_m (optional, device): a distance per record
 // for the near bodies' distanceM.  pairs: recs are the change's n pairs (k_change.h) -- feature i is the cur half of pair i
-// with its base half's three properties
+// with its base half's three properties.  series / windows (optional, device): a span's series row per record
+// (api_span.h) for the features' windows and counts; without one every byte is as it always was
 static int gj_tiles(hm_ctx *ctx, const GjTexts &T, const GrowRec *recs, int64_t n, int32_t out_memory, const uint8_t **bytes,
-                    const int64_t **offsets, const double *dist_m = nullptr, bool pairs = false) {
+                    const int64_t **offsets, const double *dist_m = nullptr, bool pairs = false, const int64_t *series = nullptr,
+                    int windows = 0) {
     hm_ctx::GeoJson &G = ctx->gj;
     int rc;
     if ((rc = gj_init(ctx))) return rc;
@@ -103,7 +105,7 @@ static int gj_tiles(hm_ctx *ctx, const GjTexts &T, const GrowRec *recs, int64_t 
     HIPCHK(ctx, hipMemsetAsync(words, 0, GJW_WORDS * 8, ctx->stream));
     HIPCHK(ctx, hipEventRecord(G.ev[0], ctx->stream));
     hipLaunchKernelGGL(k_gj_tile_sizes, dim3(read_grid(ctx->read_grid, n, 256)), dim3(256), 0, ctx->stream, T, recs, n, vlat, vlng, (int *)G.vn.p,
-                       (unsigned *)G.sizes.p, words, dist_m, pairs ? 2 : 1, pairs);
+                       (unsigned *)G.sizes.p, words, dist_m, pairs ? 2 : 1, pairs, series, windows);
     HIPCHK(ctx, hipEventRecord(G.ev[1], ctx->stream));
     gj_scan(ctx, n);
     HIPCHK(ctx, hipGetLastError());
@@ -111,16 +113,21 @@ static int gj_tiles(hm_ctx *ctx, const GjTexts &T, const GrowRec *recs, int64_t 
     HIPCHK(ctx, hipMemcpyAsync(&total, (unsigned long long *)G.off.p + n + 1, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(&longest, words + GJW_MAX, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, ctx_sync(ctx, __LINE__));
-    const int tile_max = GJ_TILE_MAX + (dist_m ? GJ_DIST_MAX : 0) + (pairs ? GJ_BASE_MAX : 0);
+    const int tile_max = GJ_TILE_MAX + (dist_m ? GJ_DIST_MAX : 0) + (pairs ? GJ_BASE_MAX : 0) + (series ? GJ_SPAN_MAX : 0);
     if (longest == 0 || longest > (unsigned long long)tile_max)
         return set_err(ctx, HM_E_STATE, "a tile feature of %llu bytes (at most %d expected)", longest, tile_max);
     const int64_t body_len = (int64_t)total + 1;
     if ((rc = ensure(ctx, G.bytes, (size_t)body_len + 16))) return rc;
-    const size_t lds = (size_t)GJ_THREADS * ((longest + 15) & ~15ull) + 64;   // (<= 64 x 992 + 64 B: below the 64-KB default)
+    // 64 x the longest feature + 64 B.  Without a series that is <= 64 x 992 + 64 B, below the 64-KB default; with one
+    // tile_max is 1232, and a launch whose longest feature exceeds 1008 bytes (counts of 13 digits and more in most of 16
+    // windows) is refused rather than given more than 64 KB (hm_span_geojson's contract, include/mobheat.h)
+    const size_t lds = (size_t)GJ_THREADS * ((longest + 15) & ~15ull) + 64;
+    if (lds > 65536)
+        return set_err(ctx, HM_E_UNSUPPORTED, "a tile feature of %llu bytes: the encoder's workgroup holds features of at most 1008", longest);
     HIPCHK(ctx, hipEventRecord(G.ev[2], ctx->stream));
     hipLaunchKernelGGL(k_gj_tile_write, dim3(read_grid(ctx->read_grid, n, GJ_THREADS)), dim3(GJ_THREADS), lds, ctx->stream, T, recs, n,
                        (const double *)vlat, (const double *)vlng, (const int *)G.vn.p, (const unsigned long long *)G.off.p,
-                       (uint8_t *)G.bytes.p, dist_m, pairs ? 2 : 1, pairs);
+                       (uint8_t *)G.bytes.p, dist_m, pairs ? 2 : 1, pairs, series, windows);
     HIPCHK(ctx, hipEventRecord(G.ev[3], ctx->stream));
     HIPCHK(ctx, hipGetLastError());
     return gj_out(ctx, n, body_len, out_memory, bytes, offsets);

@@ -18,6 +18,15 @@ int hm_live_windows(hm_ctx *ctx, int64_t *window_start_us, int64_t *keys, int64_
     return HM_OK;
 }
 
+// the live window that starts at window_start_us: its table if it holds a key, else nullptr (rollup_on_device, and the
+// span's window selection, api_span.h)
+static const hm_ctx::Gen *live_gen(const hm_ctx *ctx, int64_t window_start_us) {
+    const hm_ctx::Gen *gen = nullptr;
+    for (const auto &g : ctx->gens)
+        if (g.wenc == wenc_of(window_start_us) && g.keys > 0) gen = &g;
+    return gen;
+}
+
 // One pass over the window's table (k_rollup) into a zeroed parent table, then the compaction (k_rollup_emit); buffers
 // of its own (ru_tab, ru_out, h_ru), so that a checkpoint dump waiting in parts_regrow stays as it is.
 // Leaves *m_out records of window window_start_us at res in ctx->ru_out (0: the window is not live); `who` names the
@@ -35,9 +44,7 @@ static int rollup_on_device(hm_ctx *ctx, int64_t window_start_us, int32_t res, c
     if (ctx->stage != 0) return set_err(ctx, HM_E_STATE, "%s between stage calls", who);
     *m_out = 0;
     if (nslots_out) *nslots_out = 0;
-    const hm_ctx::Gen *gen = nullptr;
-    for (const auto &g : ctx->gens)
-        if (g.wenc == wenc_of(window_start_us) && g.keys > 0) gen = &g;
+    const hm_ctx::Gen *gen = live_gen(ctx, window_start_us);
     if (!gen) return HM_OK;
     DevBuf &ru_tab = tab ? *tab : ctx->ru_tab, &ru_out = out ? *out : ctx->ru_out;
     HIPCHK(ctx, hipSetDevice(ctx->device));

@@ -32,6 +32,9 @@ constexpr int GJ_PREFIX_LEN = 40;    // {"type":"FeatureCollection","features":[
 // GJ_BASE_MAX more
 constexpr int GJ_DIST_MAX = 38;
 constexpr int GJ_BASE_MAX = 111;
+// with a span's series (,"windows": ,"counts":[ ] -- 11 + 11 + 1 bytes -- and at most 2 + 16 x 20 + 15 bytes of numbers and
+// commas) GJ_SPAN_MAX more
+constexpr int GJ_SPAN_MAX = 360;
 constexpr int GJ_TILE_MAX = 872;
 
 // the two window texts of a call, by value (a kernel argument)
@@ -121,16 +124,22 @@ struct GjBase {
     int64_t count, n_speed;
     double sum_speed;
 };
+// a span record's series row, as tile_feature appends it: the record's count in each of the span's windows
+struct GjSpan {
+    int windows;
+    const int64_t *counts;
+};
 
 // one tile feature from the record's fields and its boundary (vertex k at lat[k * stride], lng[k * stride]); returns
 // its length (without the separator that follows it in the body).  dist_m (optional): the record's distance from a near
 // query's point, appended as the last property ,"distanceM":<repr>; nullptr: the feature as it always was.  base
 // (optional): the cell's record in a change's base window, appended after windowEnd as
 // ,"baseCount":<int>,"baseAvgSpeedKmh":<repr>,"countChange":<int> (the average by avgSpeedKmh's rule, the change
-// count - base count as int64); nullptr: every byte as without it
+// count - base count as int64); nullptr: every byte as without it.  span (optional): the record's series row, appended
+// after windowEnd as ,"windows":<int>,"counts":[<int>,...]; nullptr: every byte as without it
 HM_HD int tile_feature(uint8_t *dst, const GjTexts &T, uint64_t cell, int64_t count, int64_t n_speed, double sum_speed,
                        int nv, const double *lat, const double *lng, int64_t stride, const double *dist_m = nullptr,
-                       const GjBase *base = nullptr) {
+                       const GjBase *base = nullptr, const GjSpan *span = nullptr) {
     JsonW w{dst, 0};
     w.lit("{\"type\":\"Feature\",\"geometry\":{\"type\":\"Polygon\",\"coordinates\":[[");
     for (int k = 0; k < nv; k++) {
@@ -169,6 +178,16 @@ HM_HD int tile_feature(uint8_t *dst, const GjTexts &T, uint64_t cell, int64_t co
         w.f64(base->n_speed == 0 ? 0.0 : base->sum_speed / (double)base->n_speed);
         w.lit(",\"countChange\":");
         w.i64(count - base->count);
+    }
+    if (span) {
+        w.lit(",\"windows\":");
+        w.i64(span->windows);
+        w.lit(",\"counts\":[");
+        for (int j = 0; j < span->windows; j++) {
+            if (j) w.u8(',');
+            w.i64(span->counts[j]);
+        }
+        w.u8(']');
     }
     if (dist_m) {
         w.lit(",\"distanceM\":");

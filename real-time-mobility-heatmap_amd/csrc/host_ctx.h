@@ -288,6 +288,18 @@ struct hm_ctx {
         bool ready = false;
         int64_t info[6] = {0, 0, 0, 0, 0, 0};   // hm_change_info
     } change;
+    // hm_span_* (api_span.h, k_span.h): the series beside the parent table (u64[slots][windows]; the table and the
+    // records are ru_tab / ru_out: a span counts as a roll-up), the emitted records' rows, the records in view, the
+    // returned records' rows when a view or a ranking moved them, the control words -- buffers of its own (the ranking
+    // is the top's).  Nothing here is allocated before the first call.
+    struct Span {
+        DevBuf series, rows, vout, frows, words;
+        void *h_recs = nullptr, *h_rows = nullptr;   // pinned host copies of the records and their rows
+        size_t h_recs_cap = 0, h_rows_cap = 0;
+        hipEvent_t ev[6] = {};    // around k_span + k_span_emit; around the view; around k_span_rows
+        bool ready = false;
+        int64_t info[7] = {0, 0, 0, 0, 0, 0, 0};   // hm_span_info
+    } span;
     DevBuf keys;                    // k_ingest's event key per row (kernels.h ekey)
     // k_ingest's fused binning (large direct-path batches): the bins' cursors (RP_BINS + 1 u32: the last stays 0, so
     // that their exclusive scan ends with the total) and the slab capacity; the slabs are parts_sorted
@@ -471,6 +483,15 @@ static void change_free(hm_ctx *ctx) {
         if (b->p) (void)hipFree(b->p);
     if (C.h_out) (void)hipHostFree(C.h_out);
     for (auto &e : C.ev)
+        if (e) (void)hipEventDestroy(e);
+}
+static void span_free(hm_ctx *ctx) {
+    hm_ctx::Span &S = ctx->span;
+    for (DevBuf *b : {&S.series, &S.rows, &S.vout, &S.frows, &S.words})
+        if (b->p) (void)hipFree(b->p);
+    if (S.h_recs) (void)hipHostFree(S.h_recs);
+    if (S.h_rows) (void)hipHostFree(S.h_rows);
+    for (auto &e : S.ev)
         if (e) (void)hipEventDestroy(e);
 }
 

@@ -23,12 +23,14 @@ __device__ __forceinline__ GjBase gj_base_of(const GrowRec &b) { return GjBase{(
 
 // pass 1: the cell's boundary, once per feature (kept for pass 2: vertex k of feature i at vlat / vlng[k * n + i]), and the
 // feature's size with its separator; sizes[0] = the prefix.  rstride: record i at recs[i * rstride] (1; 2: the cur halves
-// of the change's pairs, with_base then takes the next GrowRec as the feature's base, k_change.h)
+// of the change's pairs, with_base then takes the next GrowRec as the feature's base, k_change.h).  series (optional):
+// record i's `windows` counts at series[i * windows] (a span's records, k_span.h)
 __global__ __launch_bounds__(256) void k_gj_tile_sizes(GjTexts T, const GrowRec *__restrict__ recs, int64_t n,
                                                        double *__restrict__ vlat, double *__restrict__ vlng,
                                                        int *__restrict__ vn, unsigned *__restrict__ sizes,
                                                        unsigned long long *words, const double *__restrict__ dist_m = nullptr,
-                                                       int rstride = 1, bool with_base = false) {
+                                                       int rstride = 1, bool with_base = false,
+                                                       const int64_t *__restrict__ series = nullptr, int windows = 0) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     unsigned mx = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -42,8 +44,9 @@ __global__ __launch_bounds__(256) void k_gj_tile_sizes(GjTexts T, const GrowRec 
             vlat[(int64_t)k * n + i] = k < nv ? la[k] : 0.0;
             vlng[(int64_t)k * n + i] = k < nv ? lo[k] : 0.0;
         }
+        const GjSpan gs = {windows, series ? series + i * windows : nullptr};
         const unsigned sz = (unsigned)tile_feature(nullptr, T, r.cell, (int64_t)r.count, (int64_t)r.nspeed, r.sspeed, nv, la, lo, 1,
-                                                    dist_m ? dist_m + i : nullptr, with_base ? &gb : nullptr) + 1u;
+                                                    dist_m ? dist_m + i : nullptr, with_base ? &gb : nullptr, series ? &gs : nullptr) + 1u;
         sizes[i + 1] = sz;
         mx = sz > mx ? sz : mx;
     }
@@ -60,7 +63,8 @@ __global__ __launch_bounds__(GJ_THREADS) void k_gj_tile_write(GjTexts T, const G
                                                               const int *__restrict__ vn,
                                                               const unsigned long long *__restrict__ off,
                                                               uint8_t *__restrict__ out, const double *__restrict__ dist_m = nullptr,
-                                                              int rstride = 1, bool with_base = false) {
+                                                              int rstride = 1, bool with_base = false,
+                                                              const int64_t *__restrict__ series = nullptr, int windows = 0) {
     extern __shared__ __attribute__((aligned(16))) uint8_t gj_buf[];   // GJ_THREADS x (the longest feature) + 64
     for (int64_t b0 = (int64_t)blockIdx.x * GJ_THREADS; b0 < n; b0 += (int64_t)gridDim.x * GJ_THREADS) {
         const int64_t b1 = b0 + GJ_THREADS < n ? b0 + GJ_THREADS : n;
@@ -73,8 +77,9 @@ __global__ __launch_bounds__(GJ_THREADS) void k_gj_tile_write(GjTexts T, const G
             GjBase gb = {0, 0, 0.0};
             if (with_base) gb = gj_base_of(recs[i * rstride + 1]);
             uint8_t *at = gj_buf + (off[i + 1] - base);
+            const GjSpan gs = {windows, series ? series + i * windows : nullptr};
             const int len = tile_feature(at, T, r.cell, (int64_t)r.count, (int64_t)r.nspeed, r.sspeed, vn[i], vlat + i, vlng + i, n,
-                                         dist_m ? dist_m + i : nullptr, with_base ? &gb : nullptr);
+                                         dist_m ? dist_m + i : nullptr, with_base ? &gb : nullptr, series ? &gs : nullptr);
             at[len] = i == n - 1 ? ']' : ',';
         }
         if (threadIdx.x == 0) {

@@ -20,6 +20,7 @@
 //   k_top.h         read side: the k records with the largest count in rank order (k_top_keys, k_top_hist, k_top_rank)
 //   k_near.h        read side: the records nearest a point within a radius (k_near_distances, k_pos_emit_near, k_near_tiles)
 //   k_change.h      read side: two windows' roll-ups joined on the cell, ranked by their count change (k_change_match, k_change_rest, k_change_keys)
+//   k_span.h        read side: a trailing span of windows rolled up in one launch, with each parent's count per window (k_span, k_span_emit, k_span_rows)
 //   k_within.h      read side: polygon geofences -- points, positions and tile centroids inside zones (k_points_in_zones, k_pos_within, k_within_tiles)
 //   host_ctx.h      the context, allocation, per-window tables, launchers;  host_batch.h: the batch phases
 //   api_*.h         the C ABI of include/mobheat.h (batch, UDF/read side, stage API, checkpoint, sink, JSON, window reads, positions, GeoJSON, viewport, self-tests)
@@ -103,6 +104,7 @@ static hipError_t upload_tables() {
 #include "k_top.h"
 #include "k_near.h"
 #include "k_change.h"
+#include "k_span.h"
 #include "k_within.h"
 #include "host_ctx.h"
 #include "host_batch.h"
@@ -125,6 +127,7 @@ extern "C" {
 #include "api_top.h"
 #include "api_near.h"
 #include "api_change.h"
+#include "api_span.h"
 #include "api_within.h"
 #include "api_selftest.h"
 

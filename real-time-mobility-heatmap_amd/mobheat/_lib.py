@@ -246,6 +246,12 @@ SIGNATURES = {
     "hm_selftest_window_change": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i32, c_i64, c_vp, _P(c_i64)]),
     "hm_selftest_change_features": (c_i32, [_P(HmGeojsonCfg), c_vp, c_i64, c_vp, c_i64, c_vp]),
     "hm_change_info": (c_i32, [c_vp, c_vp, c_i32]),
+    "hm_span_rollup": (c_i32, [c_vp, c_i64, c_i32, c_i32, _P(HmView), c_i64, c_i32, _P(c_vp), _P(c_vp), _P(c_i64)]),
+    "hm_span_geojson": (c_i32, [c_vp, c_i64, c_i32, c_i32, _P(HmGeojsonCfg), _P(HmView), c_i64, c_i32, _P(c_vp), _P(c_vp), _P(c_i64)]),
+    "hm_span_raster": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, _P(c_vp), _P(c_vp)]),
+    "hm_span_info": (c_i32, [c_vp, c_vp, c_i32]),
+    "hm_selftest_span": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_i32, c_vp, c_vp, _P(c_i64)]),
+    "hm_selftest_span_features": (c_i32, [_P(HmGeojsonCfg), c_vp, c_vp, c_i32, c_i64, c_vp, c_i64, c_vp]),
     "hm_test_read_grid_info": (c_i32, [c_vp, c_vp, c_vp, c_vp]),
     "hm_selftest_float_repr_host": (c_i32, [c_vp, c_i64, c_vp, c_vp]),
     "hm_selftest_float_repr_device": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32]),
@@ -818,6 +824,49 @@ def change_features_selftest(pairs, window_start_text, window_end_text):
     offs = np.zeros(pairs.size + 1, np.int64)
     check(lib.hm_selftest_change_features(ctypes.byref(cfg), ptr(pairs) if pairs.size else None, pairs.size, ptr(buf), cap, ptr(offs)),
           None, "hm_selftest_change_features")
+    return buf[:geojson_body_len(offs)].copy(), offs
+
+
+# ---- a trailing span of live windows (csrc/k_span.h) ----
+HM_SPAN_MAX_WINDOWS = 16
+
+
+def span_rows_at(p, n, windows, copy=True):
+    """n series rows at host pointer p as int64[n, windows] (a copy, or a view of the library's buffer)."""
+    if n == 0:
+        return np.zeros((0, int(windows)), np.int64)
+    rows = np.ctypeslib.as_array(ctypes.cast(p, _P(ctypes.c_int64)), shape=(n * int(windows),)).reshape(n, int(windows))
+    return rows.copy() if copy else rows
+
+
+def span_selftest(per_window_records, first_us, tile_us, res):
+    """Host execution of the span (no GPU) on one STATE_REC_DTYPE array per window of the span, in window order:
+    (records sorted by cell, series int64[n, windows])."""
+    lib = load()
+    per = [np.ascontiguousarray(r, dtype=STATE_REC_DTYPE) for r in per_window_records]
+    counts = np.array([r.size for r in per], np.int64)
+    recs = np.concatenate(per) if per else np.zeros(0, STATE_REC_DTYPE)
+    out = np.zeros(max(recs.size, 1), STATE_REC_DTYPE)
+    series = np.zeros((max(recs.size, 1), max(len(per), 1)), np.int64)
+    n = c_i64()
+    check(lib.hm_selftest_span(ptr(recs) if recs.size else None, ptr(counts) if counts.size else None, len(per), int(first_us),
+                               int(tile_us), int(res), ptr(out), ptr(series), ctypes.byref(n)), None, "hm_selftest_span")
+    return out[:n.value].copy(), series[:n.value].copy()
+
+
+def span_features_selftest(recs, series, window_start_text, window_end_text):
+    """Host execution of the GPU encoder on a span's STATE_REC_DTYPE records and their series rows (no GPU): (body uint8,
+    offsets int64)."""
+    lib = load()
+    recs = np.ascontiguousarray(recs, dtype=STATE_REC_DTYPE)
+    series = np.ascontiguousarray(series, dtype=np.int64)
+    assert series.ndim == 2 and series.shape[0] == recs.size
+    cfg, keep = geojson_cfg(window_start_text, window_end_text)
+    cap = 64 + (920 + 24 + 21 * series.shape[1]) * recs.size
+    buf = np.zeros(cap, np.uint8)
+    offs = np.zeros(recs.size + 1, np.int64)
+    check(lib.hm_selftest_span_features(ctypes.byref(cfg), ptr(recs) if recs.size else None, ptr(series) if recs.size else None,
+                                        series.shape[1], recs.size, ptr(buf), cap, ptr(offs)), None, "hm_selftest_span_features")
     return buf[:geojson_body_len(offs)].copy(), offs
 
 

@@ -810,6 +810,66 @@ class HeatmapEngine:
         check(self._lib.hm_change_info(self._ctx, v, 6), self._ctx, "hm_change_info")
         return {"cur_cells": v[0], "base_cells": v[1], "both": v[2], "in_view": v[3], "returned": v[4], "device_us": v[5]}
 
+    # ---- a trailing span of live windows as one heatmap with per-window counts (hm_span_*; csrc/k_span.h) ----
+    def _span_args(self, end_start_us, windows, res, view, k):
+        if end_start_us is None:
+            ws, _ = self.live_windows()
+            end_start_us = ws[-1] if ws.size else 0
+        v = None if view is None else _lib.view_struct(view)
+        return (int(end_start_us), int(windows), self.h3_res if res is None else int(res), v,
+                None if v is None else ctypes.byref(v), -1 if k is None else int(k))
+
+    def window_span(self, end_start_us=None, windows=1, res=None, view=None, k=None, copy=True):
+        """The `windows` (1..16) consecutive windows ending with the one that starts at end_start_us (None: the newest
+        live one) as one heatmap at resolution res <= h3_res (None: h3_res): (records, series) -- STATE_REC_DTYPE
+        records, one per cell that any live window of the span holds, count / n_speed / sums added up over the windows,
+        window_start_us the span's first window; series int64[n, windows], row i the count of record i's cell in each
+        window of the span (0 where the window is not live or lacks the cell; the row adds up to the count).  All
+        windows are aggregated on the GPU in one launch (hm_span_rollup), in no particular order.  view=(west, south,
+        east, north): only the cells in view; k (0..65536): the k busiest of them in rank order (window_top's).
+        copy=False: views of the library's pinned buffers, valid until the next call on this engine.  On a shard engine:
+        the rank's partial records, unranked only."""
+        end, windows, res, v, vp, kk = self._span_args(end_start_us, windows, res, view, k)
+        if k is not None and kk < 0:
+            raise ValueError(f"k = {kk} outside 0..{_lib.HM_TOP_MAX}")
+        p, ps, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        check(self._lib.hm_span_rollup(self._ctx, end, windows, res, vp, kk, HM_MEM_HOST, ctypes.byref(p), ctypes.byref(ps),
+                                       ctypes.byref(n)), self._ctx, "hm_span_rollup")
+        return _lib.state_recs_at(p, n.value, copy), _lib.span_rows_at(ps, n.value, windows, copy)
+
+    def window_span_geojson(self, end_start_us=None, windows=1, res=None, view=None, k=None, tz=None, copy=True):
+        """window_span's records as the body of a /api/tiles/span route: window_geojson's feature of every record
+        (windowStart: the span's first window's start, windowEnd: its last window's end) with "windows" and "counts" --
+        the record's series row -- after windowEnd, aggregated and encoded on the GPU (hm_span_geojson).  Unranked, the
+        features come in the aggregation's order."""
+        end, windows, res, v, vp, kk = self._span_args(end_start_us, windows, res, view, k)
+        if k is not None and kk < 0:
+            raise ValueError(f"k = {kk} outside 0..{_lib.HM_TOP_MAX}")
+        first = end - (windows - 1) * self.tile_us
+        cfg, keep = _lib.geojson_cfg(_lib.wall_iso(first, tz), _lib.wall_iso(end + self.tile_us, tz))
+        pb, po, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+        check(self._lib.hm_span_geojson(self._ctx, end, windows, res, ctypes.byref(cfg), vp, kk, HM_MEM_HOST, ctypes.byref(pb),
+                                        ctypes.byref(po), ctypes.byref(n)), self._ctx, "hm_span_geojson")
+        return self._geojson_body(pb, po, n.value, copy)
+
+    def window_span_raster(self, lat, lon, end_start_us=None, windows=1, res=None, thresholds=None, copy=True):
+        """window_raster of the span's summed counts: counts uint32[rows, cols] over the grid lat[rows] x lon[cols], or
+        (counts, classes) with thresholds (hm_span_raster)."""
+        end, windows, res, _, _, _ = self._span_args(end_start_us, windows, res, None, None)
+        lat, lon, thr = _lib.raster_args(lat, lon, thresholds)
+        pc, pk = ctypes.c_void_p(), ctypes.c_void_p()
+        check(self._lib.hm_span_raster(self._ctx, end, windows, res, ptr(lat), lat.size, ptr(lon), lon.size,
+                                       None if thr is None else ptr(thr), 0 if thr is None else thr.size, HM_MEM_HOST,
+                                       ctypes.byref(pc), ctypes.byref(pk) if thr is not None else None),
+              self._ctx, "hm_span_raster")
+        return _lib.raster_grids(pc, pk, lat, lon, thr, copy)
+
+    def span_info(self):
+        v = (ctypes.c_int64 * 7)()
+        check(self._lib.hm_span_info(self._ctx, v, 7), self._ctx, "hm_span_info")
+        return {"live_windows": v[0], "keys": v[1], "parents": v[2], "in_view": v[3], "returned": v[4], "table_slots": v[5],
+                "device_us": v[6]}
+
     # ---- radius queries: the vehicles / tiles nearest a point (hm_*_near; csrc/k_near.h) ----
     def positions_near(self, lat, lon, max_distance_m=float("inf"), k=_lib.HM_TOP_MAX, since_us=None, copy=True):
         """The k vehicles of the positions state nearest (lat, lon) within max_distance_m metres (closed; inf: no limit),

@@ -476,6 +476,122 @@ def tiles_change_body(engine, window_start_us=None, base_start_us=None, res=None
     return engine.window_change_geojson(window_start_us, base_start_us, res, view, order, k, tz)
 
 
+# ---- a trailing span of live windows: one heatmap with per-window counts (HeatmapEngine.window_span, csrc/k_span.h) ----
+SPAN_MAX_WINDOWS = _lib.HM_SPAN_MAX_WINDOWS
+
+
+def cell_to_parent(cells, res):
+    """upstream cellToParent for res <= every cell's resolution, in numpy: the resolution field becomes res, the digits
+    past res become 7"""
+    cells = np.asarray(cells, dtype=np.uint64)
+    res = int(res)
+    unused = np.uint64((1 << (3 * (15 - res))) - 1)
+    return (cells & ~np.uint64(0xF << 52)) | np.uint64(res << 52) | unused
+
+
+def span_of(per_window_records, first_us, tile_us, res):
+    """span(...) in numpy from one STATE_REC_DTYPE array per window of the span, in window order (window j starts at
+    first_us + j * tile_us; an empty array: a window that is not live): (records sorted by cell, series int64[n, windows])
+    -- the parent of every record at res, a group-by on it adding count, n_speed and the three sums, window_start_us =
+    first_us, and per parent its count in each window.  The comparison form of HeatmapEngine.window_span."""
+    per = [np.asarray(r, dtype=_lib.STATE_REC_DTYPE) for r in per_window_records]
+    if not 1 <= len(per) <= SPAN_MAX_WINDOWS:
+        raise ValueError(f"{len(per)} windows outside 1..{SPAN_MAX_WINDOWS}")
+    recs = np.concatenate(per)
+    col = np.repeat(np.arange(len(per)), [r.size for r in per])
+    cells, inv = np.unique(cell_to_parent(recs["cell"], res), return_inverse=True)
+    out = np.zeros(cells.size, _lib.STATE_REC_DTYPE)
+    out["cell"], out["window_start_us"] = cells, int(first_us)
+    for f in ("count", "n_speed"):
+        np.add.at(out[f], inv, recs[f])
+    for f in ("sum_speed", "sum_lat", "sum_lon"):
+        out[f] = np.bincount(inv, weights=recs[f], minlength=cells.size)
+    series = np.zeros((cells.size, len(per)), np.int64)
+    np.add.at(series, (inv, col), recs["count"])
+    return out, series
+
+
+def span_windows(tile_us, minutes=None, windows=None):
+    """the span's length in windows: `windows` itself, or ceil(minutes / the window's minutes); one of the two"""
+    if (minutes is None) == (windows is None):
+        raise ValueError("a span takes minutes or windows, one of them")
+    if windows is None:
+        us = int(round(float(minutes) * 60_000_000))
+        windows = max(1, -(-us // int(tile_us)))
+    windows = int(windows)
+    if not 1 <= windows <= SPAN_MAX_WINDOWS:
+        raise ValueError(f"{windows} windows outside 1..{SPAN_MAX_WINDOWS}")
+    return windows
+
+
+def tiles_span_collection(records, series, window_start, window_end, device=0):
+    """The FeatureCollection of a span's records, in their order: tiles_latest_collection's feature of every record
+    (windowStart / windowEnd: the two datetimes given) with windows and counts -- its series row -- after windowEnd."""
+    records = np.asarray(records, dtype=_lib.STATE_REC_DTYPE)
+    series = np.asarray(series, dtype=np.int64)
+    assert series.ndim == 2 and series.shape[0] == records.size
+    docs = [{"cellId": format(int(r["cell"]), "x"), "count": int(r["count"]),
+             "avgSpeedKmh": float(r["sum_speed"] / r["n_speed"]) if r["n_speed"] else 0.0,
+             "windowStart": window_start, "windowEnd": window_end} for r in records]
+    fc = tiles_latest_collection(docs, device)
+    for f, row in zip(fc["features"], series):
+        f["properties"]["windows"] = int(row.size)
+        f["properties"]["counts"] = [int(c) for c in row]
+    return fc
+
+
+def _span_end(engine, end_start_us):
+    if end_start_us is not None:
+        return int(end_start_us)
+    ws, _ = engine.live_windows()
+    return int(ws[-1]) if ws.size else 0
+
+
+def tiles_span_from_engine(engine, minutes=None, windows=None, res=None, view=None, k=None, tz=None, end_start_us=None):
+    """The FeatureCollection a /api/tiles/span?minutes=&res=&bbox=&n= route returns, built here from one window_records
+    call per window: the trailing span -- the newest live window is its end (or end_start_us), windows = ceil(minutes /
+    the window's minutes) -- through span_of, the view (cells_in_view) and the order (top_order).  Unranked, the features
+    are sorted by cell.  The comparison form of tiles_span_body."""
+    import datetime as _dt
+
+    from .stream import _spark_datetime
+
+    def when(us):
+        if tz is None:
+            return _spark_datetime(us)
+        return _dt.datetime.fromtimestamp(us // 1000000, tz).replace(tzinfo=None, microsecond=us % 1000000)
+    w = span_windows(engine.tile_us, minutes, windows)
+    end = _span_end(engine, end_start_us)
+    first = end - (w - 1) * engine.tile_us
+    live = set(engine.live_windows()[0].tolist())
+    per = [engine.window_records(first + j * engine.tile_us, engine.h3_res) if first + j * engine.tile_us in live
+           else np.zeros(0, _lib.STATE_REC_DTYPE) for j in range(w)]
+    recs, series = span_of(per, first, engine.tile_us, engine.h3_res if res is None else res)
+    if view is not None:
+        keep = cells_in_view(recs["cell"], view, engine.device)
+        recs, series = recs[keep], series[keep]
+    if k is not None:
+        order = top_order(recs["count"], recs["cell"], k)
+        recs, series = recs[order], series[order]
+    return tiles_span_collection(recs, series, when(first), when(end + engine.tile_us), engine.device)
+
+
+def tiles_span_body(engine, minutes=None, windows=None, res=None, view=None, k=None, tz=None, end_start_us=None):
+    """The response body of a /api/tiles/span route as bytes, the span's windows aggregated, filtered, ranked and encoded
+    on the GPU in one call (HeatmapEngine.window_span_geojson); unranked, the features come in the aggregation's order."""
+    w = span_windows(engine.tile_us, minutes, windows)
+    return engine.window_span_geojson(_span_end(engine, end_start_us), w, res, view, k, tz)
+
+
+def tiles_span_png(engine, z, x, y, minutes=None, windows=None, res=None, size=256, end_start_us=None):
+    """What a /api/tiles/span/{z}/{x}/{y}.png route returns: tile z/x/y of the trailing span's summed counts as an indexed
+    PNG in the reference page's count classes, as tiles_latest_png."""
+    w = span_windows(engine.tile_us, minutes, windows)
+    lat, lon = tile_grid(z, x, y, size)
+    _, classes = engine.window_span_raster(lat, lon, _span_end(engine, end_start_us), w, res, COUNT_THRESHOLDS, copy=False)
+    return png_from_classes(classes, COUNT_PALETTE)
+
+
 # ---- radius queries: what is around a point, nearest first (HeatmapEngine.positions_near / window_near, csrc/k_near.h) ----
 EARTH_RADIUS_M = _lib.HM_EARTH_RADIUS_M   # MongoDB's sphere
 _DEG = 0.017453292519943295               # the double math.radians multiplies by
